@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- sector HxV throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A "step" = one full product Hv = H v of the BASELINE C3 sector (cdn_hm_2dsquare: 2x2 cluster +
@@ -193,6 +193,52 @@ def time_other_workload(name, dev, reps):
     return out
 
 
+DUMP_SAMPLE = 1 << 21   # --dump-outputs: at most this many entries of Hv over all ranks (16 B each as float64 re/im: 32 MB), a fixed seeded sample
+
+
+def seeded_slab(sec, seed, dev):
+    """This rank's columns of the input vector in the padded device layout.  The numbers are drawn in the REFERENCE's order (column by
+    column of DimUp entries, in chunks of a fixed number of columns) and laid out by sec.pad (pitch, device row order), so that the input
+    is the same vector whatever layout a build gives the sector: two builds can be compared output for output."""
+    import torch
+
+    g = torch.Generator(device=dev).manual_seed(seed)
+    q = sec.localElems // sec.pitch
+    v = torch.zeros(sec.localElems, dtype=torch.complex128, device=dev)
+    chunk = max(1, (1 << 26) // sec.DimUp)
+    for c0 in range(0, q, chunk):
+        nc = min(chunk, q - c0)
+        x = torch.complex(torch.randn(nc * sec.DimUp, dtype=torch.float64, device=dev, generator=g),
+                          torch.randn(nc * sec.DimUp, dtype=torch.float64, device=dev, generator=g))
+        v[c0 * sec.pitch: (c0 + nc) * sec.pitch] = sec.pad(x, nc)
+        del x
+    return v
+
+
+def dump_outputs(sec, hv_local, out_dir, rank, world):
+    """--dump-outputs: this rank's slab of Hv as a caller of the product receives it, in the reference's order (sec.unpad), as float64 [n, 2]
+    (re, im) in DIR/hv.npy (DIR/hv_rank<r>.npy with several ranks).  A slab longer than its share of DUMP_SAMPLE is sampled at fixed seeded
+    positions (sorted, the same for every build of the same sector)."""
+    import numpy as np
+    import torch
+
+    n_ref = (sec.localElems // sec.pitch) * sec.DimUp
+    share = max(1, DUMP_SAMPLE // world)
+    if n_ref <= share:
+        hv = sec.unpad(hv_local)[:n_ref]
+    else:
+        idx = np.sort(np.random.default_rng(20240807 + rank).choice(n_ref, size=share, replace=False))
+        col, row = idx // sec.DimUp, idx % sec.DimUp
+        if sec.row_perm is not None:
+            pos, sign = col * sec.pitch + sec.row_perm[row], sec.row_sign[row].astype(np.float64)
+        else:
+            pos, sign = col * sec.pitch + row, np.ones(len(idx))
+        hv = hv_local[torch.from_numpy(pos.astype(np.int64)).to(hv_local.device)] * torch.from_numpy(sign).to(hv_local.device)
+    a = torch.view_as_real(hv.contiguous()).cpu().numpy().astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "hv.npy" if world == 1 else f"hv_rank{rank}.npy"), a)
+
+
 def exchange_link_figures(sec, world, exchange):
     """(bytes one GPU receives per product, link-bound ms) of an open split sector under `exchange` (xGMI is point to point --
     every peer's bytes arrive over that peer's own link, 153 GB/s each way, 7 links per GPU -- so the bound is the LARGEST per-peer ingest
@@ -241,7 +287,12 @@ def main():
     ap.add_argument("--no-apply-host", action="store_true", help="skip the host-array leg (N=1): hxv_apply_host with its two PCIe copies against the box's own link rates (config.apply_host)")
     ap.add_argument("--no-check", action="store_true", help="N>1: skip the one checked product before the warm-up (split vs unsplit product on every rank)")
     ap.add_argument("--check", action="store_true", help="(kept for old command lines: the check is the default now)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the product of the last one, as its caller receives it (reference order), to DIR/hv.npy "
+                         "(float64 [n, 2] = re, im; a fixed seeded sample of at most 2^21 entries; DIR/hv_rank<r>.npy per rank with N>1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -293,8 +344,7 @@ def main():
     hxv.set_exchange_default("allgather")
     Dim, Nloc = sec.Dim, sec.localElems   # Nloc: local vector length in the padded device layout (include/hxv.h)
     g = torch.Generator(device=dev).manual_seed(1234 + rank)
-    v_local = torch.randn(Nloc, dtype=torch.float64, device=dev, generator=g) + 1j * torch.randn(Nloc, dtype=torch.float64, device=dev, generator=g)
-    torch.view_as_real(v_local).view(-1, sec.pitch, 2)[:, sec.DimUp:, :] = 0.0   # (pad rows are zero in every device vector)
+    v_local = seeded_slab(sec, 1234 + rank, dev)   # (pad rows are zero in every device vector)
     hv_local = torch.empty(Nloc, dtype=torch.complex128, device=dev)
     if multi and not by_sector and world > 1 and sec.exchange_mode != args.exchange and (capi_exchange or args.exchange == "halo"):
         # (the spH0nd block keeps the all-gather exchange in mode 2; tiny sectors keep it too): report what actually runs
@@ -391,6 +441,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ms_step = dt / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(sec, hv_local, args.dump_outputs, rank, world)   # (the last timed step's product, before the legs below reuse hv_local)
     value = (world if by_sector else 1) * 32.0 * Dim / (ms_step * 1e-3) / 1e9   # sectors: every rank finished a whole product
 
     # roofline of the product's kernels on this rank: HIP events on the stream they are launched on

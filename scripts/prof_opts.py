@@ -1,6 +1,6 @@
 """Target of rocprofv3 runs: apply an option set ("k=v,k=v") to the C3 sector (WORKLOAD env: C2..C5) and run nrep products."""
 import os, sys
-sys.path.insert(0, "/root/repo/cdmft-lanc-ed_amd")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cdmft-lanc-ed_amd"))
 import torch, hxv
 from hxv import models
 wl = os.environ.get("WORKLOAD", "C3")

@@ -1,7 +1,8 @@
 #!/bin/bash
-# usage: prof_sq.sh <tag> "<options>" : SQ / LDS / TCP counters of the product kernels -> gpurun_out/sq_<tag>/summary.txt
+# usage: prof_sq.sh <tag> "<options>" : SQ / LDS / TCP counters of the product kernels -> prof_out/sq_<tag>/summary.txt
 TAG=$1; OPTS=$2
-OUT=/root/repo/gpurun_out/sq_$TAG
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+OUT=$ROOT/prof_out/sq_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 i=0
@@ -10,7 +11,7 @@ for PMC in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_WRITE_REQ_sum TCP_PENDING_STALL_CYCLES_sum" \
            "TA_BUSY_avr TA_TA_BUSY_sum TCP_GATE_EN1_sum TCP_GATE_EN2_sum" "GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $OUT/pmc$i -- python3 /root/repo/scripts/prof_opts.py "$OPTS" 2 > $OUT/pmc$i.log 2>&1 || echo "pmc pass $i failed" >> $OUT/errors.log
+  rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $OUT/pmc$i -- python3 $ROOT/scripts/prof_opts.py "$OPTS" 2 > $OUT/pmc$i.log 2>&1 || echo "pmc pass $i failed" >> $OUT/errors.log
 done
 python3 - $OUT <<'PY' > $OUT/summary.txt
 import csv, glob, os, sys
