@@ -503,6 +503,7 @@ int slab_from_host(hxv_handle* h, const void* v_host, double2* d_vec) {
   if (s.qdw <= 0) return HXV_OK;
   if (!s.row_order()) {
     HIPCHK(hipMemcpy2DAsync(d_vec, pit, v_host, col, col, (size_t)s.qdw, hipMemcpyHostToDevice, h->stream));
+    if (pit > col) HIPCHK(hipMemset2DAsync(d_vec + s.dimup, pit, 0, pit - col, (size_t)s.qdw, h->stream));  // (pad rows are zero in every device vector)
     HIPCHK(hipStreamSynchronize(h->stream));
   } else {
     double2* tmp = nullptr;

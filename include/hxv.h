@@ -240,7 +240,8 @@ int32_t hxv_pitch(const hxv_handle *h);
  *                       vectors are [DimDw columns][pitch = roundup8(nrows)].
  * hxv_apply_dw_panel  : d_y = d_x H_dw^T, same layout in and out.
  * hxv_apply_up_add    : d_hv_local = D.v + H_up v + d_w on the local slab; d_v_local and d_w are [qdw columns][pitch]
- *                       (d_v_local = this rank's slab only -- no gathered vector); not available with spH0nd (Jx/Jp). */
+ *                       (d_v_local = this rank's slab only -- no gathered vector); not available with spH0nd (Jx/Jp).
+ * Like the product, both halves never read the pad rows of their inputs and never write the pad rows of their outputs. */
 int hxv_create_dw_panel(const hxv_model *model, int32_t nup, int32_t ndw, int32_t nrows, int32_t device, hxv_handle **out);
 int hxv_apply_dw_panel(hxv_handle *panel, const void *d_x, void *d_y, void *stream);
 int hxv_apply_up_add(hxv_handle *h, const void *d_v_local, const void *d_w, void *d_hv_local, void *stream);
@@ -376,7 +377,7 @@ int hxv_apply_ladder_axpy(hxv_handle *from, hxv_handle *to, int32_t orbital, int
 int hxv_vector_alloc(hxv_handle *h, void **d_vec);
 int hxv_vector_alloc_many(hxv_handle *h, int32_t count, void **d_vec); /* `count` vectors in one allocation, hxv_localvec_elems() apart: the d_evecs of hxv_eigh_lowest; freed as one */
 int hxv_vector_free(hxv_handle *h, void *d_vec);
-int hxv_vector_from_host(hxv_handle *h, const void *v_host, void *d_vec);
+int hxv_vector_from_host(hxv_handle *h, const void *v_host, void *d_vec); /* writes every element of d_vec: pad rows zero, whatever it held */
 int hxv_vector_to_host(hxv_handle *h, const void *d_vec, void *v_host);
 
 /* ---- device-buffer cache.  A fresh hipMalloc costs ~25 ms per GB on this platform (0.7 s for the 28 GB Krylov basis of

@@ -9,14 +9,20 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def test_fortran_host_through_procedure_pointer(built):
-    from hxv import models
-    from oracle.oracle import OracleSector
-
+@pytest.fixture(scope="module")
+def fortran_demo(built):
+    """One run of the demo host per module: every test below checks its own lines of the same captured output."""
     exe = built.build_fortran()
     if exe is None:
         pytest.skip("flang not available")
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    return subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+
+
+def test_fortran_host_through_procedure_pointer(fortran_demo):
+    from hxv import models
+    from oracle.oracle import OracleSector
+
+    out = fortran_demo
     assert out.returncode == 0, out.stdout + out.stderr
     txt = out.stdout
     e0_c1 = float(re.search(r"C1 plaquette.*E0=\s*([-\d.Ee+]+)", txt).group(1))
@@ -42,7 +48,7 @@ def test_fortran_host_through_procedure_pointer(built):
     assert abs(e0_tri - e0_c2) < 1e-9 and abs(e0_eig - e0_c2) < 1e-9 and abs(dn) < 1e-10
 
 
-def test_fortran_gpu_sp_eigh_wrapper(built):
+def test_fortran_gpu_sp_eigh_wrapper(fortran_demo):
     """gpu_sp_eigh(MatVec,eval,evec,Nblock,Nitermax,tol) -- SciFortran's sp_eigh signature, ED_DIAG.f90:152-160 -- called from
     the Fortran demo host on C2: two lowest eigenvalues vs scipy ARPACK on the oracle's matrices, residual of the 2nd pair."""
     import scipy.sparse.linalg as sla
@@ -50,10 +56,7 @@ def test_fortran_gpu_sp_eigh_wrapper(built):
     from oracle.oracle import OracleSector
     from helpers_matrix import oracle_full_matrix
 
-    exe = built.build_fortran()
-    if exe is None:
-        pytest.skip("flang not available")
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    out = fortran_demo
     assert out.returncode == 0, out.stdout + out.stderr
     m2 = re.search(r"C2 device sp_eigh E=\s*([-\d.Ee+]+)\s+([-\d.Ee+]+)\s+resid2=\s*([-\d.Ee+]+)", out.stdout)
     assert m2, out.stdout
@@ -63,14 +66,11 @@ def test_fortran_gpu_sp_eigh_wrapper(built):
     assert np.abs(e - ref).max() < 1e-9 and float(m2.group(3)) < 1e-8
 
 
-def test_fortran_mpi_branch_call_text(built):
+def test_fortran_mpi_branch_call_text(fortran_demo):
     """The reference's MpiStatus=T call lines (ED_DIAG.f90:152-156,176-177; ED_GF_NORMAL.f90:215: communicator first) compile
     against the glue's generic interfaces and run through the engine's own communicator (one rank: RCCL all-gather /
     all-reduce execute); the numbers equal the serial branch."""
-    exe = built.build_fortran()
-    if exe is None:
-        pytest.skip("flang not available")
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    out = fortran_demo
     assert out.returncode == 0, out.stdout + out.stderr
     txt = out.stdout
     ser = re.search(r"C2 device sp_eigh E=\s*([-\d.Ee+]+)\s+([-\d.Ee+]+)", txt)
@@ -82,13 +82,10 @@ def test_fortran_mpi_branch_call_text(built):
     assert abs(e_l - float(ser.group(1))) < 1e-9 and abs(e_t - float(ser.group(1))) < 1e-8
 
 
-def test_fortran_paired_tridiagonalisation(built):
+def test_fortran_paired_tridiagonalisation(fortran_demo):
     """gpu_sp_lanc_tridiag_pair: two channels of ED_GF_NORMAL.f90:123-306 on one product, called from the Fortran demo host;
     both lowest Ritz values equal the ground state, and channel a equals its own single run."""
-    exe = built.build_fortran()
-    if exe is None:
-        pytest.skip("flang not available")
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    out = fortran_demo
     assert out.returncode == 0, out.stdout + out.stderr
     txt = out.stdout
     mp = re.search(r"C2 device tridiag pair E0=\s*([-\d.Ee+]+)\s+([-\d.Ee+]+)", txt)
@@ -99,15 +96,12 @@ def test_fortran_paired_tridiagonalisation(built):
     assert abs(float(mp.group(1)) - e0) < 1e-8 and abs(float(mp.group(2)) - e0) < 1e-8
 
 
-def test_fortran_device_resident_green_function_channel(built):
+def test_fortran_device_resident_green_function_channel(fortran_demo):
     """gpu_sp_lanc_eigh_dev -> gpu_keep_sector -> gpu_apply_ladder -> gpu_sp_lanc_tridiag_dev (the three-line change of
     ED_GF_NORMAL.f90:174-217 in INTEGRATION.md): ground state, c^dagger|gs> and a 100-step tridiagonalisation with NO Dim-sized PCIe
     transfer (the engine's own h2d / d2h byte counters, hxv_get_stats), alanc / blanc equal to the host-array path -- the reference's
     serial c^dagger loop restated in the demo host + gpu_sp_lanc_tridiag on the host array, which does move vectors."""
-    exe = built.build_fortran()
-    if exe is None:
-        pytest.skip("flang not available")
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    out = fortran_demo
     assert out.returncode == 0, out.stdout + out.stderr
     txt = out.stdout
     m = re.search(r"GF device channel: E0=\s*([-\d.Ee+]+)\s*norm2=\s*([-\d.Ee+]+).*channel-sector=\s*(\d+)\s+(\d+)\s+(\d+)\s+(\d+)", txt)
@@ -145,14 +139,11 @@ def test_fortran_device_resident_green_function_channel(built):
     assert float(dz.group(4)) < 1e-9 and float(dz.group(5)) < 1e-9
 
 
-def test_fortran_stored_matrices_binding(built):
+def test_fortran_stored_matrices_binding(fortran_demo):
     """gpu_build_Hv_sector_from_csr (the reference's spH0ups(1) / spH0dws(1) / spH0d handed over flattened) from the Fortran host: the
     matrices come out of a model-built sector through gpu_get_sector_csr / _diag, go back in through the binding, and the two products
     agree; nnz(H_up) = 8 568 is the survey's count for this model."""
-    exe = built.build_fortran()
-    if exe is None:
-        pytest.skip("flang not available")
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    out = fortran_demo
     assert out.returncode == 0, out.stdout + out.stderr
     m = re.search(r"stored matrices: nnz\(H_up\),nnz\(H_dw\)=\s*(\d+)\s+(\d+)\s*max\|Hv\(csr\)-Hv\(model\)\|=\s*([-\d.Ee+]+)\s*max\|Hv\|=\s*([-\d.Ee+]+)", out.stdout)
     assert m, out.stdout
