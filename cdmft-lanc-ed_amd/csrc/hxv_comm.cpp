@@ -432,6 +432,38 @@ int comm_allreduce_sum(hxv_handle* h, double* d_buf, size_t count, hipStream_t s
   return HXV_OK;
 }
 
+// The whole vector on every rank, in the padded all-gather layout, into a buffer of the caller's (nranks * cmax columns of pitch elements):
+// what the impurity observables read when a pair of dw configurations spans two ranks.  Independent of the exchange the products use
+// (the halo layout holds only the columns H_dw couples).  Unused slots of ranks that own one column less hold whatever was there.
+int comm_allgather_slab(hxv_handle* h, const double2* d_v_local, double2* d_full, hipStream_t st) {
+  const SectorHost& s = h->host;
+  HIPCHK(hipSetDevice(h->device));
+  const size_t cb = col_bytes(h, false), slot = (size_t)s.cmax * cb;
+  char* full = reinterpret_cast<char*>(d_full);
+  char* mine = full + (size_t)s.rank * slot;
+  if (s.qdw > 0) HIPCHK(hipMemcpyAsync(mine, d_v_local, (size_t)s.qdw * cb, hipMemcpyDeviceToDevice, st));
+  if (LocalGroup* G = lg(h)) {
+    int rc = HXV_OK;
+    h->xfer_full = d_full;
+    HIPREC(hipEventRecord(G->ready[s.rank], st));
+    if (G->barrier()) return broken_group();
+    for (int p = 0; p < s.nranks; ++p) {
+      if (p == s.rank || rc) continue;
+      HIPREC(hipStreamWaitEvent(st, G->ready[p], 0));
+      HIPREC(hipMemcpyAsync(full + (size_t)p * slot, reinterpret_cast<const char*>(G->member[p]->xfer_full) + (size_t)p * slot, slot, hipMemcpyDefault, st));
+    }
+    HIPREC(hipEventRecord(G->done[s.rank], st));
+    if (G->barrier()) return broken_group();
+    for (int p = 0; p < s.nranks; ++p)
+      if (p != s.rank) HIPREC(hipStreamWaitEvent(st, G->done[p], 0));  // my buffer stays put until every peer has read my slab
+    return rc;
+  }
+  if (!h->comm) return fail(HXV_ERR_STATE, "whole-vector gather without a communicator");
+  ncclResult_t e = api(h)->AllGather(mine, full, slot / sizeof(double), ncclFloat64, (ncclComm_t)h->comm, st);
+  if (e != ncclSuccess) return comm_failed(h, "ncclAllGather", e);
+  return HXV_OK;
+}
+
 // Collective error agreement: every rank passes its local status; all return non-zero if any rank failed.  Called by the
 // drivers after their rank-local preparations (allocations, argument checks) and BEFORE their first collective, so that a
 // rank that cannot go on does not leave its peers waiting inside an all-reduce.

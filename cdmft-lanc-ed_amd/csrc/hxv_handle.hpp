@@ -5,6 +5,7 @@
 #include <atomic>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -25,6 +26,8 @@ bool comm_in_gather(const hxv_handle* h, const void* p);  // p lies in one of th
 int comm_allreduce_sum(hxv_handle* h, double* d_buf, size_t count, hipStream_t st);  // no-op without a communicator
 int comm_sendrecv_cols(hxv_handle* h, const void* send, const int64_t* send_ptr, void* recv, const int64_t* recv_ptr, size_t col_bytes, hipStream_t st);
 int comm_agree(hxv_handle* h, int rc_local);  // collective: non-zero on every rank if any rank passes non-zero (no-op without a communicator)
+// this rank's slab -> d_full, every rank's slab at column slot rank*cmax (the padded all-gather layout, whatever exchange mode h uses)
+int comm_allgather_slab(hxv_handle* h, const double2* d_v_local, double2* d_full, hipStream_t st);
 // (H v)|slab from this rank's slab: exchange + product; `ep`: optional Lanczos epilogue of pass A (its partial sums are this rank's share)
 int apply_slab(hxv_handle* h, const double2* d_v_local, double2* d_hv_local, hipStream_t st, const LzEpilogue* ep = nullptr);
 int apply_slab_real(hxv_handle* h, const double* d_v_local, double* d_hv_local, hipStream_t st, const LzEpilogue* ep = nullptr);
@@ -101,6 +104,10 @@ struct SectorImage {
   // tables and the device pointers they will be patched into
   struct Pending;
   std::shared_ptr<Pending> pending;
+  // the pair and bin tables of the impurity observables (hxv_observables.hip), built on the first hxv_observables_accumulate
+  struct ObsTables;
+  std::shared_ptr<ObsTables> obs;
+  std::mutex obs_mu;
   ~SectorImage();
 };
 // the cache of closed sectors' images (hxv_cache.cpp); an empty key means "do not cache"
@@ -174,6 +181,7 @@ struct hxv_handle {
   void* lgroup = nullptr;        // thread ranks of one process (hxv_comm_init_local): the group object, see hxv_comm.cpp
   const char* xfer_send = nullptr;         // thread ranks: what this rank offers in the column exchange under way (comm_sendrecv_cols)
   const int64_t* xfer_send_ptr = nullptr;  //               and its per-destination offsets
+  const double2* xfer_full = nullptr;      // thread ranks: the whole-vector buffer of comm_allgather_slab under way
   double2* d_gather = nullptr;   // nranks * cmax * pitch elements (all-gather layout) / (qdw + halo) * pitch (halo layout)
   double2* d_gather_x[2] = {nullptr, nullptr};  // two more of the same for the device Lanczos on a split sector (three vectors rotate)
   double2* gather_cur = nullptr; // the gather buffer the exchange under way / last done runs on (peers of a thread group read it)

@@ -50,6 +50,9 @@ module ED_HAMILTONIAN_GPU_HXV
   public :: gpu_sector_nnz
   public :: gpu_get_sector_csr
   public :: gpu_get_sector_diag
+  !impurity observables of device-resident states (ED_OBSERVABLES.f90 lanc_observables / lanc_local_energy / single-particle density matrix)
+  public :: gpu_observables_dev
+  public :: gpu_get_observables
 
   !> A vector that lives on the device, in the layout of the sector it was made for.  Opaque: pass it back to the gpu_* routines.
   type :: gpu_vector
@@ -299,9 +302,31 @@ module ED_HAMILTONIAN_GPU_HXV
      type(c_ptr) function hxv_last_error() bind(C,name="hxv_last_error")
        import :: c_ptr
      end function hxv_last_error
+     integer(c_int64_t) function hxv_obs_record_elems(h) bind(C,name="hxv_obs_record_elems")
+       import :: c_int64_t, c_ptr
+       type(c_ptr),value :: h
+     end function hxv_obs_record_elems
+     integer(c_int) function hxv_observables_accumulate(h,d_psi,weight,accumulate,record) bind(C,name="hxv_observables_accumulate")
+       import :: c_int, c_int32_t, c_ptr, c_double
+       type(c_ptr),value        :: h,d_psi
+       real(c_double),value     :: weight
+       integer(c_int32_t),value :: accumulate
+       real(c_double)           :: record(*)
+     end function hxv_observables_accumulate
+     integer(c_int64_t) function hxv_obs_derived_elems(model) bind(C,name="hxv_obs_derived_elems")
+       import :: c_int64_t, hxv_model
+       type(hxv_model),intent(in) :: model
+     end function hxv_obs_derived_elems
+     integer(c_int) function hxv_observables_derive(model,record,out) bind(C,name="hxv_observables_derive")
+       import :: c_int, c_double, hxv_model
+       type(hxv_model),intent(in) :: model
+       real(c_double),intent(in)  :: record(*)
+       real(c_double)             :: out(*)
+     end function hxv_observables_derive
   end interface
 
   type(c_ptr),save :: handle = c_null_ptr   !one open sector at a time (ED_HAMILTONIAN_COMMON.f90:17-18)
+  real(c_double),allocatable,save :: obs_record(:)   !the summed raw record of gpu_observables_dev (include/hxv.h)
 
 contains
 
@@ -937,5 +962,75 @@ contains
     real(8),intent(in),optional :: threshold
     call gpu_sp_lanc_tridiag_serial(MatVec,vin,alanc,blanc,threshold)
   end subroutine gpu_sp_lanc_tridiag_mpi
+
+  !> One state of state_list (ED_OBSERVABLES.f90:110-140) into the module's summed record: vect is a device vector (gpu_sp_eigh_dev /
+  !! gpu_sp_lanc_eigh_dev) on its own sector -- the open one, or one kept open for it by gpu_keep_sector, as gpu_apply_ladder takes it --
+  !! peso the reference's weight exp(-beta(Ei-Egs))/zeta_function.  accumulate=.false. starts a new sum (the first state), .true. adds to
+  !! it.  On a split sector every rank calls it with its slab and holds the global record.
+  subroutine gpu_observables_dev(vect,peso,accumulate)
+    type(gpu_vector),intent(in) :: vect
+    real(8),intent(in)          :: peso
+    logical,intent(in)          :: accumulate
+    integer(c_int64_t)          :: n
+    if(.not.vec_alive(vect))stop "gpu_observables_dev ERROR: empty vector, or its sector was closed under it (gpu_keep_sector keeps it open)"
+    n=hxv_obs_record_elems(vect%sector)
+    if(n<=0)stop "gpu_observables_dev ERROR: the open sector has no impurity record (Nimp > 10, or no basis maps)"
+    if(accumulate)then
+       if(.not.allocated(obs_record))stop "gpu_observables_dev ERROR: accumulate=.true. before a first state"
+       if(size(obs_record,kind=c_int64_t)/=n)stop "gpu_observables_dev ERROR: the record of this sector belongs to another model"
+    else
+       if(allocated(obs_record))deallocate(obs_record)
+       allocate(obs_record(n))
+    endif
+    call check(hxv_observables_accumulate(vect%sector,vect%d,real(peso,c_double),merge(1_c_int32_t,0_c_int32_t,accumulate),obs_record),&
+         "gpu_observables_dev")
+  end subroutine gpu_observables_dev
+
+  !> The named quantities of the summed record (hxv_observables_derive), shaped like the reference's: ed_dens, ed_dens_up, ed_dens_dw,
+  !! ed_docc (Nlat,Norb), ed_Eknot, ed_Epot (Ehartree included, ED_OBSERVABLES.f90:434), ed_Ehartree, ed_Dust, ed_Dund and
+  !! single_particle_density_matrix (Nlat,Nlat,Nspin,Nspin,Norb,Norb); magz, sz2, n2, s2tot optionally.  The model inputs are the module
+  !! globals the reference has in scope (ED_INPUT_VARS.f90:13-16,129-135,164; impHloc ED_VARS_GLOBAL.f90:119).  Ehartree's constant term
+  !! uses Uloc(iorb), not the reference's Uloc(is) (:399, which reads past Norb): include/hxv.h.
+  subroutine gpu_get_observables(Nlat,Norb,Nspin,impHloc,Uloc,Ust,Jh,hfmode,dens,dens_up,dens_dw,docc,Eknot,Epot,Ehartree,Dust,Dund,&
+       spdm,magz,sz2,n2,s2tot)
+    integer,intent(in)                      :: Nlat,Norb,Nspin
+    complex(8),intent(in),target,contiguous :: impHloc(:,:,:,:,:,:)   ![Nlat,Nlat,Nspin,Nspin,Norb,Norb]
+    real(8),intent(in)                      :: Uloc(5),Ust,Jh
+    logical,intent(in)                      :: hfmode
+    real(8),intent(out)                     :: dens(Nlat,Norb),dens_up(Nlat,Norb),dens_dw(Nlat,Norb),docc(Nlat,Norb)
+    real(8),intent(out)                     :: Eknot,Epot,Ehartree,Dust,Dund
+    complex(8),intent(out)                  :: spdm(Nlat,Nlat,Nspin,Nspin,Norb,Norb)
+    real(8),intent(out),optional            :: magz(Nlat,Norb),sz2(Nlat,Nlat,Norb,Norb),n2(Nlat,Nlat,Norb,Norb),s2tot(Nlat)
+    type(hxv_model)                         :: m
+    real(c_double),allocatable              :: out(:)
+    integer(c_int64_t)                      :: n
+    integer                                 :: k,lo,llo,i
+    if(.not.allocated(obs_record))stop "gpu_get_observables ERROR: no state recorded (gpu_observables_dev)"
+    m%nlat=Nlat; m%norb=Norb; m%nspin=Nspin; m%nbath=0
+    m%hfmode=0; if(hfmode)m%hfmode=1
+    m%reserved=0
+    m%uloc=Uloc
+    m%ust=Ust; m%jh=Jh; m%jx=0d0; m%jp=0d0; m%xmu=0d0
+    m%imphloc=c_loc(impHloc); m%hbath=c_null_ptr; m%vbath=c_null_ptr
+    if(size(obs_record,kind=c_int64_t)/=4_c_int64_t**(Nlat*Norb)+4_c_int64_t*(Nlat*Norb)**2)&
+         stop "gpu_get_observables ERROR: the recorded sector belongs to another model"
+    n=hxv_obs_derived_elems(m)
+    if(n<=0)stop "gpu_get_observables ERROR: unsupported model (Nimp <= 10, Norb <= 5)"
+    allocate(out(n))
+    call check(hxv_observables_derive(m,obs_record,out),"gpu_get_observables")
+    lo=Nlat*Norb; llo=lo*lo
+    k=0
+    dens   =reshape(out(k+1:k+lo),[Nlat,Norb]); k=k+lo
+    dens_up=reshape(out(k+1:k+lo),[Nlat,Norb]); k=k+lo
+    dens_dw=reshape(out(k+1:k+lo),[Nlat,Norb]); k=k+lo
+    docc   =reshape(out(k+1:k+lo),[Nlat,Norb]); k=k+lo
+    if(present(magz))magz=reshape(out(k+1:k+lo),[Nlat,Norb]); k=k+lo
+    if(present(sz2))sz2=reshape(out(k+1:k+llo),[Nlat,Nlat,Norb,Norb]); k=k+llo
+    if(present(n2))n2=reshape(out(k+1:k+llo),[Nlat,Nlat,Norb,Norb]); k=k+llo
+    if(present(s2tot))s2tot=out(k+1:k+Nlat); k=k+Nlat
+    Eknot=out(k+1); Epot=out(k+2); Ehartree=out(k+3); Dust=out(k+4); Dund=out(k+5); k=k+5
+    spdm=reshape([(cmplx(out(k+2*i-1),out(k+2*i),kind=8),i=1,llo*Nspin*Nspin)],[Nlat,Nlat,Nspin,Nspin,Norb,Norb])
+    deallocate(out)
+  end subroutine gpu_get_observables
 
 end module ED_HAMILTONIAN_GPU_HXV

@@ -48,6 +48,7 @@ EXPORTS = [
     "hxv_comm_local_create", "hxv_comm_init_local", "hxv_comm_local_destroy", "hxv_comm_local_abort", "hxv_time_apply_slab",
     "hxv_vector_alloc", "hxv_vector_alloc_many", "hxv_vector_free", "hxv_vector_from_host", "hxv_vector_to_host",
     "hxv_sector_cache_clear", "hxv_sector_cache_stats", "hxv_comm_abort", "hxv_comm_library", "hxv_comm_cache_stats", "hxv_comm_cache_clear", "hxv_host_register", "hxv_host_unregister",
+    "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
 ]
 
 _lib = None
@@ -152,6 +153,12 @@ def load_library():
     L.hxv_host_unregister.argtypes = [vp]
     L.hxv_live_handles.argtypes = []
     L.hxv_live_handles.restype = i64
+    L.hxv_obs_record_elems.argtypes = [vp]
+    L.hxv_obs_record_elems.restype = i64
+    L.hxv_observables_accumulate.argtypes = [vp, vp, dbl, i32, pd]
+    L.hxv_obs_derived_elems.argtypes = [C.POINTER(_Model)]
+    L.hxv_obs_derived_elems.restype = i64
+    L.hxv_observables_derive.argtypes = [C.POINTER(_Model), pd, pd]
     _lib = L
     return L
 
@@ -837,6 +844,26 @@ class HxvSector:
         _chk(load_library().hxv_apply_ladder_axpy(self._h, to._h, orbital, spin, int(bool(create)), cf.real, cf.imag, int(accumulate),
                                                   psi.data_ptr(), out.data_ptr(), C.byref(n2)), "hxv_apply_ladder_axpy")
         return (to.unpad(out) if (contiguous and not accumulate) else out), n2.value
+
+    def observables_record(self, psi_device, weight: float = 1.0, out: np.ndarray | None = None, accumulate: bool = False) -> np.ndarray:
+        """Raw impurity-observables record of one device-resident state (include/hxv.h, hxv_observables_accumulate): W, R_up, R_dw as
+        float64, weighted by `weight` (the reference's peso).  psi_device: a device vector of this sector in the padded layout (localElems
+        complex128 elements: this rank's slab on a split sector, collective there).  With accumulate=True the state's record is added to
+        `out`.  Feed the record to hxv.observables.derive."""
+        import torch
+
+        assert psi_device.is_cuda and psi_device.dtype == torch.complex128 and psi_device.is_contiguous() and psi_device.numel() == self.localElems, \
+            "observables_record takes a device vector in the padded layout (localElems elements)"
+        L = load_library()
+        n = L.hxv_obs_record_elems(self._h)
+        if out is None:
+            assert not accumulate, "accumulate=True needs `out`"
+            out = np.zeros(max(n, 1))
+        assert out.dtype == np.float64 and out.flags.c_contiguous and (n == 0 or out.size == n)
+        torch.cuda.synchronize(psi_device.device)
+        _chk(L.hxv_observables_accumulate(self._h, psi_device.data_ptr(), float(weight), int(bool(accumulate)), _p(out, C.c_double)),
+             "hxv_observables_accumulate")
+        return out
 
     def time_lanczos(self, nrep: int) -> float:
         import torch

@@ -367,6 +367,37 @@ int hxv_apply_ladder(hxv_handle *from, hxv_handle *to, int32_t orbital, int32_t 
 int hxv_apply_ladder_axpy(hxv_handle *from, hxv_handle *to, int32_t orbital, int32_t spin, int32_t create, double coef_re,
                           double coef_im, int32_t accumulate, const void *d_psi, void *d_out, double *norm2);
 
+/* ---- impurity observables of device-resident states --------------------------------------------------------------------------
+ * ED_OBSERVABLES.f90 lanc_observables (:94-236), lanc_local_energy (:246-452) and the single-particle density matrix of
+ * density_matrix_impurity (:609-686), without the eigenvector on the host.  The impurity orbitals are the low Nimp = Nlat*Norb bits of
+ * each spin's configuration (is = iorb + ilat*Norb, 0-based; ED_SETUP.f90:563-568), and every quantity of those routines is a function of
+ * one RAW RECORD per state, hxv_obs_record_elems() doubles:
+ *   [0, 4^Nimp)                         W[a_up + 2^Nimp*a_dw]  weight * |psi|^2 summed over the basis states with impurity bits a_up, a_dw
+ *                                                              (= the diagonal of the reference's cluster_density_matrix)
+ *   [4^Nimp, 4^Nimp + 2*Nimp^2)          R_up(is,js)  complex, is fastest: weight * sum sgn1*sgn2 * psi_i * conj(psi_j), |j> = c^+_is c_js |i>
+ *                                                     (the reference's convention, :644-666); R_up(is,is) = weight * sum n_is |psi_i|^2
+ *   [4^Nimp + 2*Nimp^2, + 4*Nimp^2)      R_dw(is,js)  the same for spin dw
+ * hxv_observables_accumulate: d_psi is a device vector of h (this rank's slab in the padded layout, device row order included; pad rows are
+ * never read).  accumulate == 0 overwrites record, otherwise adds weight * (this state's record) to it; weight is the reference's peso
+ * (exp(-beta(Ei-Egs)) / zeta_function, ED_OBSERVABLES.f90:134-135).  Runs on the handle's stream and returns once the record is on the
+ * host.  The same vector on the same handle gives the same bits on every call (no floating-point atomics).  Split sectors (after
+ * hxv_comm_init / _init_local): collective, every rank returns the GLOBAL record (replaces the Bcast_MPI of :226-233 / :424-430), and all
+ * ranks fail together.  Errors: HXV_ERR_ARG for NULL arguments; HXV_ERR_STATE for a handle without basis maps (from CSR, a dw panel);
+ * HXV_ERR_UNSUPPORTED for Nimp > 10 (a record over 8 MB).  hxv_obs_record_elems returns 0 for such handles.                          */
+int64_t hxv_obs_record_elems(const hxv_handle *h);
+int hxv_observables_accumulate(hxv_handle *h, const void *d_psi, double weight, int32_t accumulate, double *record /* host */);
+/* The reference's named quantities from a record (pure host code, no device), hxv_obs_derived_elems doubles in this order, each in the
+ * reference's Fortran array order:
+ *   dens, dens_up, dens_dw, docc, magz (Nlat,Norb);  sz2, n2 (Nlat,Nlat,Norb,Norb);  s2tot (Nlat);
+ *   Eknot, Epot (Ehartree included, as :434), Ehartree, Dust, Dund;
+ *   single_particle_density_matrix complex (Nlat,Nlat,Nspin,Nspin,Norb,Norb), only ispin == jspin <= Nspin written (:633-666).
+ * The fill pattern is the reference's: sz2 / n2 hold (ilat,ilat,iorb,iorb) and, for every jlat, the jorb > iorb pairs and their transposes;
+ * Eknot is the real part of its complex sum; the Ust / Jh terms apply for Norb > 1 only.  ONE DELIBERATE DIVERGENCE: Ehartree's constant
+ * term uses uloc(iorb) where the reference reads uloc(is) with is = imp_state_index (:399) -- past Norb, and for Nimp > 5 past the 5-element
+ * Uloc (ED_INPUT_VARS.f90:19); uloc(iorb) is the intent of the commented line at :395.  Needs Nimp <= 10, Norb <= 5.                    */
+int64_t hxv_obs_derived_elems(const hxv_model *model);
+int hxv_observables_derive(const hxv_model *model, const double *record, double *out);
+
 /* ---- device vectors owned by the library --------------------------------------------------------------------------------
  * For host programs without a HIP binding of their own (the Fortran glue): a local vector of the handle's sector in the padded device
  * layout (hxv_localvec_elems() complex elements, zeroed), from the engine's buffer cache.  Such a pointer is what the device drivers take
