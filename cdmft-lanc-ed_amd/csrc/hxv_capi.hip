@@ -302,6 +302,10 @@ int hxv_create_from_csr(int32_t dimup, int32_t dimdw, const int64_t* up_rowptr, 
 int hxv_set_nonlocal_csr(hxv_handle* h, const int64_t* rowptr, const int32_t* cols, const double* vals) {
   if (!h || !rowptr) return fail(HXV_ERR_ARG, "hxv_set_nonlocal_csr: NULL argument");
   if (h->host.panel_rows > 0) return fail(HXV_ERR_STATE, "hxv_set_nonlocal_csr: not on a panel handle");
+  // only for hxv_create_from_csr handles: their rows are the reference's and they own their image.  A model handle (basis maps) may store
+  // its rows in a device row order the stored block does not know, and shares its image with every other open of the sector (cache).
+  if (!h->host.map_up.empty() || !h->host.map_dw.empty() || h->host.row_order())
+    return fail(HXV_ERR_STATE, "hxv_set_nonlocal_csr: only for handles opened with hxv_create_from_csr (a model handle builds its own spH0nd block)");
   if (h->host.nd.active) return fail(HXV_ERR_STATE, "hxv_set_nonlocal_csr: the handle already has an spH0nd block");
   if (h->host.exchange != 0) return fail(HXV_ERR_UNSUPPORTED, "hxv_set_nonlocal_csr: the spH0nd block needs the whole gathered vector (all-gather exchange)");
   const int64_t nloc = (int64_t)h->host.qdw * h->host.dimup;

@@ -1174,16 +1174,17 @@ int hxv_apply_ladder_axpy(hxv_handle* from, hxv_handle* to, int32_t orbital, int
   //  * spin dw: target column j of sector B is (a sign times) ONE column of sector A, which may belong to another rank of A's split:
   //    a column permutation.  Every rank derives from the two dw maps what it needs from whom and what everybody needs from it
   //    (deterministic, no negotiation), packs, exchanges once, and assembles.
+  // a dw operator keeps the row: the two sectors -- same nup, same model -- must store their rows in the same order, split or not
+  if (spin == 1 && (a.row_order() != b.row_order() || (a.row_order() && a.up_pos != b.up_pos)))
+    return fail(HXV_ERR_STATE, "hxv_apply_ladder: the two sectors store their rows in different orders (HXV_ROW_ORDER changed between the opens?)");
   if (!accumulate) HIPCHK(hipMemsetAsync(d_out, 0, (size_t)b.pitch * std::max(b.qdw, 1) * sizeof(double2), st));  // pad rows = 0
   if (spin == 0 || !split) {
     // spin up with a device row order (SectorHost::up_perm): the source row is looked up in the source sector's SORTED reference map and sent
-    // through its permutation; `to`'s map is by device row already; both basis signs ride along.  A dw operator keeps the row, and the two
-    // sectors -- same nup, same model -- have the same row order: nothing to do.
+    // through its permutation; `to`'s map is by device row already; both basis signs ride along.  A dw operator keeps the row (same row
+    // order on both sides, checked above): nothing to do.
     const uint32_t* mf = spin == 0 ? (a.row_order() ? from->dev.map_up_ref : from->dev.diag.map_up) : from->dev.diag.map_dw;
     const uint32_t* mt = spin == 0 ? to->dev.diag.map_up : to->dev.diag.map_dw + b.dw0;  // (dw: the local target columns)
     if (spin == 0 && a.qdw != b.qdw) return fail(HXV_ERR_STATE, "hxv_apply_ladder: the DimDw splits of the two sectors differ");
-    if (spin == 1 && (a.row_order() != b.row_order() || (a.row_order() && a.up_pos != b.up_pos)))
-      return fail(HXV_ERR_STATE, "hxv_apply_ladder: the two sectors store their rows in different orders (HXV_ROW_ORDER changed between the opens?)");
     hipError_t e = launch_ladder(mf, spin == 0 ? a.dimup : a.dimdw, mt, spin == 0 ? b.dimup : b.dimdw, a.pitch, b.dimup, b.pitch, b.qdw,
                                  orbital, spin, create ? 1 : 0, (const double2*)d_psi, (double2*)d_out, st, coef, accumulate ? 1 : 0,
                                  spin == 0 ? from->dev.up_perm : nullptr, spin == 0 ? from->dev.up_sign : nullptr, spin == 0 ? to->dev.up_sign : nullptr);

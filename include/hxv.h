@@ -72,7 +72,8 @@ int hxv_create_from_csr(int32_t dimup, int32_t dimdw, const int64_t *up_rowptr, 
  * ED_HAMILTONIAN_SPARSE_HxV.f90:217-225 serial / :298-312 MPI): the LOCAL rows (vecDim of them) with GLOBAL 1-based column indices
  * i = iup + (idw-1)*DimUp, rowptr[vecDim+1] 0-based offsets, vals interleaved complex.  Applied as its own pass over Hv after the
  * product, from the gathered vector (all-gather exchange only).  Once per handle; not on handles opened from a model with
- * Jx / Jp (those build the block themselves).  Dim < 2^31 (the reference's column type).                                  */
+ * Jx / Jp (those build the block themselves).  Dim < 2^31 (the reference's column type).
+ * HXV_ERR_STATE on any handle not opened with hxv_create_from_csr (a model handle's rows may be in a device row order).    */
 int hxv_set_nonlocal_csr(hxv_handle *h, const int64_t *rowptr, const int32_t *cols, const double *vals);
 
 /* delete_Hv_sector (ED_HAMILTONIAN.f90:149-190). NULL is a no-op. */
@@ -358,7 +359,9 @@ int hxv_time_lanczos(hxv_handle *h, void *d_work3 /* 3*hxv_localvec_elems() comp
  * every rank builds its own slab of the new vector -- the master-only loop + scatter of ED_GF_NORMAL.f90:174-214 is gone.
  * A spin-up operator is local to a slab (both sectors share DimDw and its split); a spin-dw operator maps whole columns of
  * one split onto the other: every rank derives from the two dw maps what it needs from whom and what the others need from it,
- * and one column exchange moves them.  *norm2 is the GLOBAL <out|out>.                                                        */
+ * and one column exchange moves them.  *norm2 is the GLOBAL <out|out>.
+ * A spin-dw operator keeps the row, so HXV_ERR_STATE (split or not, d_out untouched) when the two sectors store their rows in
+ * different device row orders (HXV_ROW_ORDER or its hooks changed between the opens).                                         */
 int hxv_apply_ladder(hxv_handle *from, hxv_handle *to, int32_t orbital, int32_t spin, int32_t create, const void *d_psi,
                      void *d_out, double *norm2);
 /* Mixed channels (ED_GF_NORMAL.f90:370-406 (c^dagger_i + c^dagger_j)|gs>, :746-780 (c^dagger_i + xi c^dagger_j)|gs>, and the

@@ -3,7 +3,9 @@ order the up configurations take when the orbitals are renumbered, with the sign
 so that pass A's out-of-block gathers are contiguous runs.  Everything the reference sees keeps ITS order.  Checked against the CPU oracle
 (the reference's order throughout) on sectors small enough for it, with the test hooks that switch the order on below its size threshold:
 the product through host arrays and through device vectors, both kernels, the Lanczos drivers, the ladder operators between two sectors,
-the spH0nd block, real vectors, the introspection calls; and that the order is a relabelling (a permutation, +-1 signs, H_dev = S P H P^T S)."""
+the spH0nd block, real vectors, the introspection calls -- on real and complex H, with and without spH0nd, every case in a non-identity order;
+and that the order is a relabelling (a permutation, +-1 signs, H_dev = S P H P^T S).  Two calls that cannot honour an order are refused: a stored
+spH0nd block on a model handle, a dw ladder operator between sectors whose orders differ.  tests/test_gpu_row_order_sweep.py: random models."""
 import numpy as np
 import pytest
 
@@ -38,7 +40,6 @@ def _rel(a, b):
 @pytest.mark.parametrize("name", ["C2", "star", "bhz", "kanamori"])
 def test_product_in_device_row_order_matches_the_oracle(built, row_order, name):
     import torch
-    import hxv
     from hxv import models
     from oracle.oracle import OracleSector
 
@@ -48,23 +49,18 @@ def test_product_in_device_row_order_matches_the_oracle(built, row_order, name):
     elif name == "star":
         m, (nup, ndw) = models.hm_2dsquare(Nbath=2, xmu=0.2), (5, 7)            # Ns = 12: the C3 geometry with two replicas
     elif name == "bhz":
-        m, (nup, ndw) = models.bhz_2d(Nbath=0, Ust=0.4, Jh=0.1), (4, 4)
-        bits = 5
+        # complex H (Nspin = 2, H_up != H_dw) at Ns = 12: with 8 block bits the low orbitals are not sorted by their ties to the high ones
+        # (at Ns = 8 without a bath, 5 bits would leave them sorted: the identity, the reference's order)
+        m, (nup, ndw) = models.bhz_2d(Nx=2, Ny=1, Nbath=2, Ust=0.4, Jh=0.1), (6, 5)
     else:
-        m, (nup, ndw) = models.bhz_2d(Nbath=0, Ust=0.7, Jh=0.2, Jx=0.2, Jp=0.15), (3, 5)
-        bits = 5
-    if bits != 8:
-        import os
-        os.environ["HXV_ROW_ORDER_BITS"] = str(bits)
-        hxv.sector_cache_clear()
+        # the same with Jx / Jp: the spH0nd block's move tables by device row, folded into pass A and as its own pass
+        m, (nup, ndw) = models.bhz_2d(Nx=2, Ny=1, Nbath=2, Ust=0.7, Jh=0.2, Jx=0.2, Jp=0.15), (5, 5)
     sec = _open(m, nup, ndw, bits)
     orc = OracleSector(m, nup, ndw)
-    if name in ("C2", "star"):
-        assert sec.row_perm is not None, "the hook did not switch the row order on"
-    if sec.row_perm is not None:
-        # a relabelling: a permutation of the rows and a sign per basis vector
-        assert sorted(sec.row_perm.tolist()) == list(range(sec.DimUp)) and set(np.unique(sec.row_sign).tolist()) <= {-1, 1}
-        assert not np.array_equal(sec.row_perm, np.arange(sec.DimUp))
+    # a relabelling, and not the identity: a permutation of the rows and a sign per basis vector
+    assert sec.row_perm is not None, "the hook did not switch the row order on"
+    assert sorted(sec.row_perm.tolist()) == list(range(sec.DimUp)) and set(np.unique(sec.row_sign).tolist()) <= {-1, 1}
+    assert not np.array_equal(sec.row_perm, np.arange(sec.DimUp))
     # what the reference sees keeps its order: maps, stored matrices, diagonal
     mu, md = sec.maps()
     assert np.array_equal(mu, orc.map_up()) and np.array_equal(md, orc.map_dw())
@@ -82,6 +78,13 @@ def test_product_in_device_row_order_matches_the_oracle(built, row_order, name):
         sec.set_option("kernel", kern)
         hv = sec.apply_device(dv)
         assert _rel(sec.unpad(hv).cpu().numpy(), ref) < TOL, kern              # device vectors: pad / unpad carry the order and the signs
+    if name == "kanamori":                                                     # spH0nd folded into pass A and as its own pass, both kernels
+        for kern in (1, 0):
+            for fold in (1, 0):
+                sec.set_option("kernel", kern)
+                sec.set_option("fold_nd", fold)
+                assert _rel(sec.unpad(sec.apply_device(dv)).cpu().numpy(), ref) < TOL, (kern, fold)
+        sec.set_option("fold_nd", 1)
     sec.set_option("kernel", 1)
     # library-owned vectors and the host <-> device copies
     back = sec.vector_to_host(sec.vector_from_host(v))
@@ -116,9 +119,12 @@ def test_product_in_device_row_order_matches_the_oracle(built, row_order, name):
         a_p, b_p = orc.lanc_tridiag(vb / np.linalg.norm(vb), 16)
         assert np.abs(aa[:8] - a_o[:8]).max() < 1e-10 and np.abs(ab[:8] - a_p[:8]).max() < 1e-10
         assert np.abs(ba[:8] - b_o[:8]).max() < 1e-10 and np.abs(bb[:8] - b_p[:8]).max() < 1e-10
-    a, b, n = sec.lanczos_tridiag(sec.pad(torch.from_numpy(v).cuda()), 20)
     ao, bo = orc.lanc_tridiag(v, 20)
-    assert np.abs(a[:10] - ao[:10]).max() < 1e-10 and np.abs(b[:10] - bo[:10]).max() < 1e-10
+    for fused in ((1, 0) if name == "kanamori" else (1,)):                    # (the fused recurrence covers the spH0nd block too)
+        sec.set_option("lanczos_fused", fused)
+        a, b, n = sec.lanczos_tridiag(sec.pad(torch.from_numpy(v).cuda()), 20)
+        assert np.abs(a[:10] - ao[:10]).max() < 1e-10 and np.abs(b[:10] - bo[:10]).max() < 1e-10, fused
+    sec.set_option("lanczos_fused", 1)
     ah, bh, _ = sec.lanczos_tridiag_host(v, 20)
     assert np.abs(ah[:10] - ao[:10]).max() < 1e-10
     if sec.real_vectors_available:
@@ -312,3 +318,104 @@ def test_row_order_on_split_sectors(built, row_order, exchange, monkeypatch):
         assert _rel(hv, ref[lo:hi]) < TOL
         assert np.abs(a[:8] - a_ref[:8]).max() < 1e-10 and np.abs(b[:8] - b_ref[:8]).max() < 1e-10
         assert np.abs(ou - lad_up[ulo:ulo + un]).max() < 1e-14 and np.abs(od - lad_dw[dlo:dlo + dn]).max() < 1e-14
+
+
+def test_stored_spH0nd_block_is_refused_on_a_model_handle(built, row_order):
+    """hxv_set_nonlocal_csr is for hxv_create_from_csr handles only (include/hxv.h): its block is written in the reference's rows, which a
+    model handle's device row order has permuted and sign-flipped, and a model handle shares its host description with every later open of
+    the sector (the sector cache).  Refused with HXV_ERR_STATE; the handle, and a fresh open of the same sector, keep the oracle's numbers
+    and what they offered before (real vectors, spH0nd folded into pass A)."""
+    import scipy.sparse as sp
+    import torch
+    import hxv
+    from hxv import models
+    from oracle.oracle import OracleSector
+
+    m, (nup, ndw) = models.hm_2dsquare(Nbath=2, xmu=0.1), (6, 5)              # Jx = Jp = 0: no spH0nd block of its own
+    orc = OracleSector(m, nup, ndw)
+    v = models.deterministic_vector(orc.Dim)
+    v /= np.linalg.norm(v)
+    ref = orc.spMatVec_main(v)
+
+    def check(sec):
+        assert sec.row_perm is not None and not np.array_equal(sec.row_perm, np.arange(sec.DimUp))
+        dv = sec.pad(torch.from_numpy(v).cuda())
+        for kern in (1, 0):
+            sec.set_option("kernel", kern)
+            assert _rel(sec.unpad(sec.apply_device(dv)).cpu().numpy(), ref) < TOL, kern
+        sec.set_option("kernel", 1)
+        assert _rel(sec.apply_host(v), ref) < TOL
+        assert sec.real_vectors_available
+        xr = np.real(v).copy()
+        assert _rel(sec.apply_device_real(torch.from_numpy(xr).cuda()).cpu().numpy(), np.real(orc.spMatVec_main(xr.astype(np.complex128)))) < TOL
+
+    sec = _open(m, nup, ndw, row_order)
+    check(sec)
+    rng = np.random.default_rng(11)                   # a Hermitian block with entries, in the reference's rows (local rows, global 1-based columns)
+    i, j = rng.integers(orc.Dim, size=64), rng.integers(orc.Dim, size=64)
+    z = rng.standard_normal(64) + 1j * rng.standard_normal(64)
+    B = sp.coo_matrix((z, (i, j)), shape=(orc.Dim, orc.Dim)).tocsr()
+    B = (B + B.conj().T).tocsr()
+    B.setdiag(0)
+    B.eliminate_zeros()
+    B.sort_indices()
+    assert B.nnz > 0
+    with pytest.raises(hxv.HxvError, match=r"status 3\).*hxv_create_from_csr"):
+        sec.set_nonlocal_csr(B.indptr.astype(np.int64), (B.indices + 1).astype(np.int32), B.data.astype(np.complex128))
+    check(sec)
+    sec.close()
+    again = _open(m, nup, ndw, row_order)             # through the cache: the same image
+    assert again.get_option("open_cache_hit") == 1
+    check(again)
+    again.close()
+    # what the call is for: a from_csr handle takes the same block (tests/test_gpu_parity.py checks its product)
+    fc = hxv.HxvSector.from_csr(orc.DimUp, orc.DimDw, orc.csr("up"), orc.csr("dw"), orc.diag(),
+                                nd=(B.indptr.astype(np.int64), (B.indices + 1).astype(np.int32), B.data.astype(np.complex128)))
+    assert fc.row_perm is None and not fc.real_vectors_available
+    assert _rel(fc.apply_host(v), ref + B @ v) < TOL
+    fc.close()
+
+
+def test_dw_ladder_between_sectors_in_different_row_orders_is_refused(built, row_order, monkeypatch):
+    """A dw operator keeps the row, so both sectors must store their rows in the same order: A opened with the row order forced, B (ndw + 1)
+    after the hooks changed (no order) -- refused with HXV_ERR_STATE unsplit and on 2 thread ranks (RCCL branches; the split branch moves whole columns).
+    The up operator between the same mixed pair carries each sector's own order and signs: the reference's result, bit for bit."""
+    import torch
+    import hxv
+    from hxv import models
+    from ladder_ref import apply_op
+
+    monkeypatch.setenv("HXV_RCCL_LIB", str(built.build_rccl_double()))
+    m, (nup, ndw), P = models.hm_2dsquare(Nbath=2, xmu=0.1), (6, 5), 2
+    orb_dw, orb_up = 3, 1
+    A = [_open(m, nup, ndw, row_order)] + [_open(m, nup, ndw, row_order, rank=r, nranks=P) for r in range(P)]
+    monkeypatch.setenv("HXV_ROW_ORDER_MIN_DIMUP", "100000")
+    hxv.sector_cache_clear()
+    B = [_open(m, nup, ndw + 1, row_order)] + [_open(m, nup, ndw + 1, row_order, rank=r, nranks=P) for r in range(P)]
+    C = [_open(m, nup + 1, ndw, row_order)] + [_open(m, nup + 1, ndw, row_order, rank=r, nranks=P) for r in range(P)]
+    assert all(s.row_perm is not None for s in A) and all(s.row_perm is None for s in B + C)
+    rng = np.random.default_rng(5)
+    psi = rng.standard_normal(A[0].Dim) + 1j * rng.standard_normal(A[0].Dim)
+    up_ref = apply_op(psi, A[0].maps(), C[0].maps(), orb_up, 0, True)
+    a, b, c = A[0], B[0], C[0]
+    dpsi = a.pad(torch.from_numpy(psi).cuda())
+    with pytest.raises(hxv.HxvError, match=r"status 3\).*different orders"):
+        a.apply_ladder(b, orb_dw, 1, True, dpsi, out=torch.zeros(b.localElems, dtype=torch.complex128, device="cuda"))
+    out, _ = a.apply_ladder(c, orb_up, 0, True, dpsi, out=torch.zeros(c.localElems, dtype=torch.complex128, device="cuda"))
+    assert np.array_equal(c.unpad(out).cpu().numpy(), up_ref)
+
+    def rank(r, group):
+        a, b, c = A[1 + r], B[1 + r], C[1 + r]
+        for s in (a, b, c):
+            group.join(s)
+        lo, hi = a.mpiIshift, a.mpiIshift + a.vecDim
+        slab = a.pad(torch.from_numpy(psi[lo:hi].copy()).cuda(), a.mpiQdw)
+        with pytest.raises(hxv.HxvError, match=r"status 3\).*different orders"):
+            a.apply_ladder(b, orb_dw, 1, True, slab, out=torch.zeros(b.localElems, dtype=torch.complex128, device="cuda"))
+        out, _ = a.apply_ladder(c, orb_up, 0, True, slab, out=torch.zeros(c.localElems, dtype=torch.complex128, device="cuda"))
+        return c.mpiIshift, c.vecDim, c.unpad(out).cpu().numpy()
+
+    for lo, n, got in hxv.run_ranks(P, rank, transport="rccl"):
+        assert np.array_equal(got, up_ref[lo:lo + n])
+    for s in A + B + C:
+        s.close()
