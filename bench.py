@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- sector HxV throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A "step" = one full product Hv = H v of the BASELINE C3 sector (cdn_hm_2dsquare: 2x2 cluster +
@@ -10,13 +10,17 @@ With N>1 ranks the sector is split along DimDw exactly like the reference (ED_HA
 each step exchanges the slabs over RCCL THROUGH THE C-ABI (hxv_comm_unique_id -> broadcast -> hxv_comm_init ->
 hxv_apply_device_slab: what a Fortran rank of the reference would run; --exchange allgather [default] | halo | alltoall = the
 reference's own two transposes) and every rank computes its slab (strong scaling: the sector is fixed).  --backend gloo goes
-through torch.distributed instead (hxv/distributed.py: the rehearsal twin).  Before the warm-up ONE product of a split run is checked on every
-rank against the unsplit sector (1e-13; "checked" / "check_rel_err" in the line; the run aborts otherwise; --no-check skips).  value = algorithmic GB/s of the whole job = 32 B x Dim / step time
+through torch.distributed instead (hxv/distributed.py: the rehearsal twin).  value = algorithmic GB/s of the whole job = 32 B x Dim / step time
 (read v once + write Hv once per basis state).
 
-Rank 0 prints ONE JSON line.  It also carries
+A plain run does only what `value` needs: it opens the sector, warms up, times the steps, writes --dump-outputs and prints ONE JSON line
+(rank 0).  --full measures and checks everything else as well, and the line then also carries
   roofline     : achieved/peak HBM GB/s of the product's kernels, timed with HIP events on the launch stream
+  config       : Lanczos iterations, the host-array surface, the 56 channels of a solve, C4 / C5, what each exchange would move at
+                 8 ranks (N=1); the two exchanges that were not asked for (N>1)
   cpu_baseline : the reference algorithm (oracle spMatVec_mpi_main, thread-ranks) on the host cores, N=1 only
+and before the warm-up ONE product of a split run is checked on every rank against the unsplit sector (1e-13; "checked" /
+"check_rel_err" in the line; the run aborts otherwise; --no-check skips it, --check asks for it without --full).
 """
 from __future__ import annotations
 
@@ -260,6 +264,10 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="C3", choices=["C2", "C3", "C4", "C5"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: (N>1) one checked product before the warm-up; after the "
+                         "timed steps the roofline, the CPU baseline, Lanczos, host arrays, the solve-shaped leg, C4 / C5 and the other "
+                         "exchanges (minutes at C3); the --no-* options skip single legs of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-lanczos", action="store_true", help="skip the Lanczos-iteration timing (N=1; second half of BASELINE's metric)")
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the C4 / C5 product timings reported in config.other_workloads (N=1)")
@@ -285,8 +293,8 @@ def main():
                          "processes on ONE GPU rehearse the driver's launch line through the engine's RCCL branches")
     ap.add_argument("--no-other-exchanges", action="store_true", help="N>1 through the C-ABI: do not open, check and time the two exchanges that were not asked for (config.other_exchanges)")
     ap.add_argument("--no-apply-host", action="store_true", help="skip the host-array leg (N=1): hxv_apply_host with its two PCIe copies against the box's own link rates (config.apply_host)")
-    ap.add_argument("--no-check", action="store_true", help="N>1: skip the one checked product before the warm-up (split vs unsplit product on every rank)")
-    ap.add_argument("--check", action="store_true", help="(kept for old command lines: the check is the default now)")
+    ap.add_argument("--no-check", action="store_true", help="N>1 with --full: skip the one checked product before the warm-up (split vs unsplit product on every rank)")
+    ap.add_argument("--check", action="store_true", help="N>1: run the checked product before the warm-up without --full too")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write the product of the last one, as its caller receives it (reference order), to DIR/hv.npy "
                          "(float64 [n, 2] = re, im; a fixed seeded sample of at most 2^21 entries; DIR/hv_rank<r>.npy per rank with N>1)")
@@ -343,7 +351,6 @@ def main():
         sec = hxv.HxvSector.from_model(model, nup, ndw, rank=rank, nranks=world, device=local_rank)
     hxv.set_exchange_default("allgather")
     Dim, Nloc = sec.Dim, sec.localElems   # Nloc: local vector length in the padded device layout (include/hxv.h)
-    g = torch.Generator(device=dev).manual_seed(1234 + rank)
     v_local = seeded_slab(sec, 1234 + rank, dev)   # (pad rows are zero in every device vector)
     hv_local = torch.empty(Nloc, dtype=torch.complex128, device=dev)
     if multi and not by_sector and world > 1 and sec.exchange_mode != args.exchange and (capi_exchange or args.exchange == "halo"):
@@ -390,9 +397,9 @@ def main():
             sec.apply_device(v_local, hv_local)
 
     checked, check_err = False, None
-    if multi and not by_sector and not args.no_check:
+    if multi and not by_sector and (args.full or args.check) and not args.no_check:
         # ONE product before the warm-up, checked on every rank: this rank's slab of the split product == the same slab of the
-        # unsplit product of the assembled vector (the N>1 path has never met a second GPU: the first run on a node must not be blind)
+        # unsplit product of the assembled vector (the N>1 path has never met a second GPU: a first run on a node wants --full or --check)
         step()
         cmax = -(-sec.DimDw // world)
         mine = torch.zeros(cmax * sec.pitch, dtype=torch.complex128, device=dev)
@@ -445,69 +452,70 @@ def main():
         dump_outputs(sec, hv_local, args.dump_outputs, rank, world)   # (the last timed step's product, before the legs below reuse hv_local)
     value = (world if by_sector else 1) * 32.0 * Dim / (ms_step * 1e-3) / 1e9   # sectors: every rank finished a whole product
 
-    # roofline of the product's kernels on this rank: HIP events on the stream they are launched on
-    nk = max(5, min(args.steps, 20))
-    if capi_exchange:
-        step_ev_ms, k_ms = sec.time_apply_slab(v_local, hv_local, nk)      # (collective: every rank runs the same nk products)
-    else:
-        vfull = hx.exchange(v_local) if hx is not None else (sh.gather(v_local) if sh is not None else v_local)
-        torch.cuda.synchronize()
-        k_ms = sec.time_apply(vfull, hv_local, nk)
-        step_ev_ms = None
-        del vfull
-    achieved = 32.0 * sec.vecDim / (k_ms * 1e-3) / 1e9
-    # HBM-side bytes per product come from a separate rocprofv3 --pmc collection (scripts/prof_traffic.sh ->
-    # profiles/traffic.json); the figure is only quoted for the kernel build it was collected on (its `kernels` stamp)
-    traffic, traffic_src = None, None
-    tf = ROOT / "profiles" / "traffic.json"
-    if tf.exists():
-        try:
-            tj = json.loads(tf.read_text())
-            if tj.get("workload") == args.workload and tj.get("n_gpus", 1) == world and tj.get("kernels_stamp") == KERNELS_STAMP:
-                traffic = tj.get("hbm_bytes_per_product")
-                traffic_src = f"profiles/traffic.json (rocprofv3 --pmc, kernels {KERNELS_STAMP})"
-        except Exception:
-            traffic = None
-    # the two-pass design's own floor: 80 B per basis state (pass B 32, pass A 48) at the guide's measured copy rate, 6.29 TB/s -- a FIXED
-    # yardstick (the box's own copy rate moved the fraction between runs); that rate is reported beside it
-    copy_gbs = copy_rate_gbs(dev)
-    floor_ms = 80.0 * sec.vecDim / (HBM_COPY_GBS * 1e9) * 1e3
-    # the rocprofv3 --kernel-trace summary of this command, quoted only when it was collected on THIS kernel build (profiles/kernel_trace.json)
-    trace = None
-    kt = ROOT / "profiles" / "kernel_trace.json"
-    if kt.exists():
-        try:
-            kj = json.loads(kt.read_text())
-            if kj.get("workload") == args.workload and kj.get("n_gpus", 1) == world and kj.get("kernels_stamp") == KERNELS_STAMP:
-                trace = {"file": kj.get("file"), "avg_ms": kj.get("avg_ms"), "product_ms": kj.get("product_ms")}
-        except Exception:
-            trace = None
-    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "design_floor_ms": round(floor_ms, 4), "frac_of_design_floor": round(floor_ms / k_ms, 4), "design_floor_rate_GBs": HBM_COPY_GBS,
-                "copy_rate_GBs": round(copy_gbs, 1), "kernels_stamp": KERNELS_STAMP, "rocprof_kernel_trace": trace,
-                "traffic": traffic, "traffic_source": traffic_src, "kernel": ("hxv_up_job" if sec.get_option("job_up_active") else "hxv_pass_up") + " + hxv_pass_dw (one product)", "kernel_ms": round(k_ms, 4),
-                "algorithmic_bytes": 32 * sec.vecDim}
-    if step_ev_ms is not None:
-        roofline["slab_product_ms_on_stream"] = round(step_ev_ms, 4)   # exchange + kernels of this rank, HIP events (hxv_time_apply_slab)
-        # what the exchange costs each rank: the slab product on the stream minus its kernels; min / max over the ranks
-        # (overlapped mode 2 runs pass A on a second stream BESIDE the exchange: that part of kernel_ms is not subtracted -- ADVICE r5)
-        k_ovl = sec.get_option("time_kernels_overlapped_us") * 1e-3
-        if k_ovl > 0:
-            roofline["kernel_ms_overlapped"] = round(k_ovl, 4)
-        ex_ms = step_ev_ms - (k_ms - k_ovl)
-        if multi:
-            t2 = torch.tensor([ex_ms, -ex_ms], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
-            dist.all_reduce(t2, op=dist.ReduceOp.MAX)
-            roofline["exchange_ms"] = {"this_rank": round(ex_ms, 4), "max": round(float(t2[0].item()), 4), "min": round(-float(t2[1].item()), 4)}
+    if args.full:
+        # roofline of the product's kernels on this rank: HIP events on the stream they are launched on
+        nk = max(5, min(args.steps, 20))
+        if capi_exchange:
+            step_ev_ms, k_ms = sec.time_apply_slab(v_local, hv_local, nk)      # (collective: every rank runs the same nk products)
         else:
-            roofline["exchange_ms"] = {"this_rank": round(ex_ms, 4), "max": round(ex_ms, 4), "min": round(ex_ms, 4)}
+            vfull = hx.exchange(v_local) if hx is not None else (sh.gather(v_local) if sh is not None else v_local)
+            torch.cuda.synchronize()
+            k_ms = sec.time_apply(vfull, hv_local, nk)
+            step_ev_ms = None
+            del vfull
+        achieved = 32.0 * sec.vecDim / (k_ms * 1e-3) / 1e9
+        # HBM-side bytes per product come from a separate rocprofv3 --pmc collection (scripts/prof_traffic.sh ->
+        # profiles/traffic.json); the figure is only quoted for the kernel build it was collected on (its `kernels` stamp)
+        traffic, traffic_src = None, None
+        tf = ROOT / "profiles" / "traffic.json"
+        if tf.exists():
+            try:
+                tj = json.loads(tf.read_text())
+                if tj.get("workload") == args.workload and tj.get("n_gpus", 1) == world and tj.get("kernels_stamp") == KERNELS_STAMP:
+                    traffic = tj.get("hbm_bytes_per_product")
+                    traffic_src = f"profiles/traffic.json (rocprofv3 --pmc, kernels {KERNELS_STAMP})"
+            except Exception:
+                traffic = None
+        # the two-pass design's own floor: 80 B per basis state (pass B 32, pass A 48) at the guide's measured copy rate, 6.29 TB/s -- a FIXED
+        # yardstick (the box's own copy rate moved the fraction between runs); that rate is reported beside it
+        copy_gbs = copy_rate_gbs(dev)
+        floor_ms = 80.0 * sec.vecDim / (HBM_COPY_GBS * 1e9) * 1e3
+        # the rocprofv3 --kernel-trace summary of this command, quoted only when it was collected on THIS kernel build (profiles/kernel_trace.json)
+        trace = None
+        kt = ROOT / "profiles" / "kernel_trace.json"
+        if kt.exists():
+            try:
+                kj = json.loads(kt.read_text())
+                if kj.get("workload") == args.workload and kj.get("n_gpus", 1) == world and kj.get("kernels_stamp") == KERNELS_STAMP:
+                    trace = {"file": kj.get("file"), "avg_ms": kj.get("avg_ms"), "product_ms": kj.get("product_ms")}
+            except Exception:
+                trace = None
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "design_floor_ms": round(floor_ms, 4), "frac_of_design_floor": round(floor_ms / k_ms, 4), "design_floor_rate_GBs": HBM_COPY_GBS,
+                    "copy_rate_GBs": round(copy_gbs, 1), "kernels_stamp": KERNELS_STAMP, "rocprof_kernel_trace": trace,
+                    "traffic": traffic, "traffic_source": traffic_src, "kernel": ("hxv_up_job" if sec.get_option("job_up_active") else "hxv_pass_up") + " + hxv_pass_dw (one product)", "kernel_ms": round(k_ms, 4),
+                    "algorithmic_bytes": 32 * sec.vecDim}
+        if step_ev_ms is not None:
+            roofline["slab_product_ms_on_stream"] = round(step_ev_ms, 4)   # exchange + kernels of this rank, HIP events (hxv_time_apply_slab)
+            # what the exchange costs each rank: the slab product on the stream minus its kernels; min / max over the ranks
+            # (overlapped mode 2 runs pass A on a second stream BESIDE the exchange: that part of kernel_ms is not subtracted -- ADVICE r5)
+            k_ovl = sec.get_option("time_kernels_overlapped_us") * 1e-3
+            if k_ovl > 0:
+                roofline["kernel_ms_overlapped"] = round(k_ovl, 4)
+            ex_ms = step_ev_ms - (k_ms - k_ovl)
+            if multi:
+                t2 = torch.tensor([ex_ms, -ex_ms], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
+                dist.all_reduce(t2, op=dist.ReduceOp.MAX)
+                roofline["exchange_ms"] = {"this_rank": round(ex_ms, 4), "max": round(float(t2[0].item()), 4), "min": round(-float(t2[1].item()), 4)}
+            else:
+                roofline["exchange_ms"] = {"this_rank": round(ex_ms, 4), "max": round(ex_ms, 4), "min": round(ex_ms, 4)}
 
     # FIRST CONTACT WITH N GPUs RECORDS EVERY EXCHANGE: `value` above is the exchange asked for (default: the all-gather
     # BASELINE mandates); the other two are opened, checked and timed in the same launch -- the sector re-opened under the other layout
     # (hxv_set_exchange_default), joined through hxv_comm_init (the process's communicator serves it: no second ncclCommInitRank), ONE product
     # compared with the checked product of the main exchange on every rank, then warm-up + timed steps + the kernels' share like above.
     other_exchanges = None
-    if capi_exchange and world > 1 and not args.no_other_exchanges:
+    if args.full and capi_exchange and world > 1 and not args.no_other_exchanges:
         other_exchanges = {}
         cpu_or_dev = dev if args.backend == "nccl" else "cpu"
         step()                                                   # hv_local = the main exchange's product of v_local (checked above)
@@ -604,8 +612,9 @@ def main():
                       "device_row_order": sec.row_perm is not None,
                       "parallelism": f"{world} independent sectors, one per GPU, no exchange" if by_sector else f"DimDw split x{world}" + ({"allgather": " + RCCL allgather per product", "halo": " + RCCL send/recv of the columns H_dw couples across ranks",
                                                                   "alltoall": " + 2 RCCL all-to-all transposes per product"}[args.exchange] if world > 1 else ""),
-                      "matvecs_per_s": round((world if by_sector else 1) * 1e3 / ms_step, 2)},
-           "roofline": roofline}
+                      "matvecs_per_s": round((world if by_sector else 1) * 1e3 / ms_step, 2)}}
+    if args.full:
+        out["roofline"] = roofline
     if multi and not by_sector:
         out["checked"] = checked
         out["check_rel_err"] = check_err
@@ -628,12 +637,12 @@ def main():
         if other_exchanges is not None:
             out["config"]["other_exchanges"] = other_exchanges
             out["config"]["comm_cache"] = hxv.comm_cache_stats()   # one ncclCommInitRank served every sector this process opened
-    if world == 1 and not args.rehearse_capi:
+    if args.full and world == 1 and not args.rehearse_capi:
         # what each of the three exchanges would move into one GPU per product at 8 ranks
         rp, cols, _ = sec.csr("dw")
         need8, _ = hxv.halo_plan(rp, cols - 1, sec.DimDw, 8)
         out["config"]["exchange_ingest_bytes_per_gpu_at_8_ranks"] = hxv.exchange_ingest_bytes(sec.DimUp, sec.DimDw, 8, need8)
-    if world == 1 and not args.rehearse_capi and not args.no_apply_host:
+    if args.full and world == 1 and not args.rehearse_capi and not args.no_apply_host:
         # THE DROP-IN SURFACE ITSELF: north_star keeps spHtimesV_p on HOST arrays (cc_sparse_HxV, ED_VARS_GLOBAL.f90:72-78; caller
         # ED_DIAG.f90:145,152) -- hxv_apply_host = H2D of v, the product, D2H of Hv.  Host arrays page-locked ONCE (hxv_host_register), then three
         # products; the floor beside it = the same bytes at this box's own H2D and D2H rates (plain pinned copies of the same size) + the kernels.
@@ -686,9 +695,10 @@ def main():
                                            "GBs_algorithmic": round(32.0 * sec.vecDim / t_pin / 1e9, 1)}
         except Exception as e:  # noqa: BLE001 (a leg beside the headline: reported, never fatal)
             out["config"]["apply_host"] = {"failed": str(e)}
-    if not args.no_lanczos and world == 1 and not args.rehearse_capi:
+    if args.full and not args.no_lanczos and world == 1 and not args.rehearse_capi:
         # full iterations: product + fused recurrence + 2 reductions, vectors in HBM.  Headline = complex(8) vectors, the
         # reference's data type; when H is real (C2, C3) the device drivers also run on real vectors (half the bytes).
+        g = torch.Generator(device=dev).manual_seed(1234 + rank)
         sec.set_option("real_vectors", 0)
         lz_ms = sec.time_lanczos(20)
         out["config"]["lanczos_ms_per_iter"] = round(lz_ms, 4)
@@ -746,7 +756,7 @@ def main():
             out["config"]["lanczos_paired_real_ms_per_iter_per_channel"] = round(pair_ms / 2, 4)
             out["config"]["lanczos_paired_real_matvecs_per_s"] = round(2e3 / pair_ms, 2)
             del va, vb
-    if world == 1 and args.workload == "C3" and not args.no_gf_solve and not args.no_lanczos and not args.rehearse_capi:
+    if args.full and world == 1 and args.workload == "C3" and not args.no_gf_solve and not args.no_lanczos and not args.rehearse_capi:
         # the callers' usage pattern as a measured whole (scripts/harness.py): ground state of (8,8) by the default spectrum call, then the
         # 56 tridiagonalisations of build_gf_normal (ED_GF_NORMAL.f90:36-110; 8 diagonal + 24 real mixed + 24 complex mixed: chan4, the
         # default), each with its sector N+-1 opened and closed around it (:208-222), device-resident, two real channels per product
@@ -771,7 +781,7 @@ def main():
                                        "H the complex channels carry nothing the real ones do not (INTEGRATION.md section 4)"}
         del recs
         torch.cuda.empty_cache()
-    if world == 1 and args.workload == "C3" and not args.no_other_workloads and not args.rehearse_capi:
+    if args.full and world == 1 and args.workload == "C3" and not args.no_other_workloads and not args.rehearse_capi:
         # the other full-size configs, driver-timed on the same GPU (parity-test sizes of BASELINE.json, not the headline)
         sec.close()
         del v_local, hv_local
@@ -787,7 +797,7 @@ def main():
                 hxv.pool_trim(local_rank)
         out["config"]["other_workloads"] = ow
         v_local = hv_local = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.rehearse_capi:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.rehearse_capi:
         sec.close()
         v_local = hv_local = None
         torch.cuda.empty_cache()

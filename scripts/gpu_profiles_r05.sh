@@ -5,8 +5,8 @@ export TMPDIR=/tmp
 PART=${PART:-1}
 if [ "$PART" = "1" ]; then
   # the driver-shaped bench line, then the same bench under rocprofv3 (kernel stats; no CPU baseline / other workloads / solve leg)
-  timeout -k 10 600 python bench.py --steps 100 --warmup 20 2> $R/bench_err.log > $R/bench_n1.json; cut -c1-400 $R/bench_n1.json
-  ( cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/$R/bench_trace -- python3 /root/repo/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-other-workloads --no-gf-solve > /root/repo/$R/bench_trace.log 2>&1 )
+  timeout -k 10 600 python bench.py --steps 100 --warmup 20 --full 2> $R/bench_err.log > $R/bench_n1.json; cut -c1-400 $R/bench_n1.json
+  ( D=$PWD; cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D/$R/bench_trace -- python3 $D/bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-other-workloads --no-gf-solve > $D/$R/bench_trace.log 2>&1 )
   cp $R/bench_trace/*/*kernel_stats.csv $R/bench_kernel_stats.csv 2>/dev/null; tail -1 $R/bench_trace.log | cut -c1-200
 fi
 if [ "$PART" = "2" ]; then

@@ -1,4 +1,4 @@
-"""bench.py's one-line JSON contract, checked on the line committed under profiles/ (the bench itself needs a GPU)."""
+"""bench.py's one-line JSON contract, checked on the line committed under profiles/ and, on a GPU, on the lines of a plain and a --full run."""
 import json
 import os
 import re
@@ -12,6 +12,7 @@ ROOT = Path(__file__).resolve().parent.parent
 
 
 def test_committed_bench_line_has_the_contract_fields():
+    """The newest line under profiles/ is a --full line: the headline fields and the legs beside it."""
     files = sorted((ROOT / "profiles").glob("r*_bench_n1_v*.json"), key=lambda p: tuple(int(x) for x in re.search(r"r(\d+)_bench_n1_v(\d+)", p.name).groups()))
     line = json.loads(files[-1].read_text().strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
@@ -109,3 +110,32 @@ def test_bench_dump_is_the_product_of_the_timed_steps(built, tmp_path):
     hv = np.load(tmp_path / "out" / "hv.npy")
     assert hv.dtype == np.float64 and hv.shape == (len(ref), 2)
     assert np.abs(hv[:, 0] + 1j * hv[:, 1] - ref).max() <= 1e-13 * np.abs(ref).max()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_measures_the_headline_only_and_full_adds_the_legs(built):
+    """A plain run sets up, warms up, times the steps and prints the headline line; roofline, CPU baseline, Lanczos, host-array and
+    exchange-volume legs come with --full only (C2 has no solve-shaped or C4 / C5 leg), and both lines state the headline alike."""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--workload", "C2", "--steps", "5", "--warmup", "2", *extra],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads(r.stdout.strip().splitlines()[-1])
+
+    plain, full = run(), run("--full")
+    assert set(plain) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                          "dtype", "data", "config"}
+    assert set(plain["config"]) == {"workload", "DimUp", "DimDw", "device_row_order", "parallelism", "matvecs_per_s"}
+    for k in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "scaling", "dtype", "data"):
+        assert plain[k] == full[k], k
+    dim = int(re.search(r"Dim=(\d+)", plain["config"]["workload"]).group(1))
+    for line in (plain, full):      # (ms_per_step is rounded to 1e-4 ms: about 0.2 % of a C2 step)
+        assert line["ms_per_step"] > 0 and abs(line["value"] / (32.0 * dim / (line["ms_per_step"] * 1e-3) / 1e9) - 1) < 5e-3
+    assert full["roofline"]["kernel_ms"] > 0 and "lanczos" in full["roofline"] and full["cpu_baseline"]["cores"] >= 1
+    for k in ("exchange_ingest_bytes_per_gpu_at_8_ranks", "apply_host", "lanczos_ms_per_iter", "lanczos_paired_real_ms_per_iter"):
+        assert k in full["config"], k
+    assert "failed" not in full["config"]["apply_host"]

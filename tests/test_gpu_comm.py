@@ -180,7 +180,7 @@ def test_bench_rehearses_the_multi_gpu_calls_with_one_rank(built, exchange):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29541", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--rehearse-capi", "--workload", "C2", "--steps", "3",
-                        "--warmup", "1", "--exchange", exchange], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--warmup", "1", "--exchange", exchange, "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["roofline"]["achieved"] > 0
@@ -207,7 +207,7 @@ def test_bench_n_processes_on_one_gpu_through_the_rccl_branches(built, exchange,
     port = {"allgather": "29581", "halo": "29582", "alltoall": "29583"}[exchange]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1", "--master-port", port,
                         os.path.join(root, "bench.py"), "--gpus", str(nproc), "--backend", "gloo", "--capi", "--workload", "C2", "--steps", "3", "--warmup", "1",
-                        "--exchange", exchange], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--exchange", exchange, "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == nproc and line["value"] > 0 and line["scaling"] == "strong"
