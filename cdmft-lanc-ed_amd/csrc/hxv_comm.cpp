@@ -478,10 +478,10 @@ int comm_agree(hxv_handle* h, int rc_local) {
     if (G->barrier()) return rc_local ? rc_local : broken_group();
   } else {
     double v = rc_local ? 1.0 : 0.0;
-    hipError_t e = hipMemcpyAsync(h->d_scalars + 7, &v, sizeof(double), hipMemcpyHostToDevice, h->stream);
+    hipError_t e = hipMemcpyAsync(h->d_scalars + LZ_AGREE, &v, sizeof(double), hipMemcpyHostToDevice, h->stream);
     ncclResult_t ne = ncclSuccess;
-    if (e == hipSuccess) ne = api(h)->AllReduce(h->d_scalars + 7, h->d_scalars + 7, 1, ncclFloat64, ncclMax, (ncclComm_t)h->comm, h->stream);
-    if (e == hipSuccess && ne == ncclSuccess) e = hipMemcpyAsync(&v, h->d_scalars + 7, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) ne = api(h)->AllReduce(h->d_scalars + LZ_AGREE, h->d_scalars + LZ_AGREE, 1, ncclFloat64, ncclMax, (ncclComm_t)h->comm, h->stream);
+    if (e == hipSuccess && ne == ncclSuccess) e = hipMemcpyAsync(&v, h->d_scalars + LZ_AGREE, sizeof(double), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && ne == ncclSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess || ne != ncclSuccess) return fail(HXV_ERR_HIP, "comm_agree: the status all-reduce failed");
     if (v != 0.0 && worst == 0) worst = HXV_ERR_STATE;

@@ -11,6 +11,9 @@
 // Everything Dim-sized stays in HBM: ncv+1 basis vectors (C3, ncv=20: 56 GB of the 288 GB).  The vector
 // kernels are plain streaming kernels (HBM-bound); per Lanczos step they read the j+1 basis vectors twice
 // (multi-dot, multi-axpy), which dominates the HxV itself -- the same trade ARPACK makes on the host.
+//
+// Shared with the single-vector drivers of hxv_lanczos.hip: the start vector (launch_init / launch_init_real) and, where the fused
+// product applies, the Lanczos step itself (lanczos_local_step).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -24,9 +27,9 @@ namespace {
 
 constexpr int JB = 8;       // basis vectors per multi-dot pass (w is re-read once per JB vectors)
 constexpr int TR_BLOCKS = 4096;  // workgroups of the streaming kernels (16 per CU)
-constexpr int MAXCV = 64;
+constexpr int MAXCV = 64;   // largest Krylov basis (the rotation keeps one element of every vector in registers)
 constexpr double DGKS_ETA2 = 0.01;  // refine when |w_after|^2 < eta^2 |w_before|^2
-constexpr double GS_TAU = 1e-13;     // projections below tau*|w| are measured but not subtracted (see gs_pass)   // largest Krylov basis (the rotation keeps one element of every vector in registers)
+constexpr double GS_TAU = 1e-13;     // projections below tau*|w| are measured but not subtracted (see gs_pass)
 
 __device__ inline double wave_sum(double x) {
   for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
@@ -127,33 +130,6 @@ __global__ void __launch_bounds__(256) tr_scale_nrm(int64_t n, double2* __restri
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
   __syncthreads();
   if (threadIdx.x == 0 && partial) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// deterministic start vector (same hash as the single-vector Lanczos in hxv_lanczos.hip): pad rows stay zero
-__global__ void __launch_bounds__(256) tr_init(int64_t n, double2* __restrict__ q, uint64_t seed, int dimup, int pitch, int col0,
-                                               const int32_t* __restrict__ iperm, const uint8_t* __restrict__ sign) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const int64_t lcol = i / pitch;
-    const int row = (int)(i - lcol * pitch);
-    const int64_t col = lcol + col0;  // global column: a split sector starts from the same vector as the unsplit one
-    if (row >= dimup) {
-      q[i] = make_double2(0.0, 0.0);
-      continue;
-    }
-    // (device row order: the vector is defined on the reference index, see lz_init)
-    const int rrow = iperm ? iperm[row] : row;
-    const double sgn = (sign && sign[row]) ? -1.0 : 1.0;
-    const uint64_t z = (uint64_t)(col * dimup + rrow) * 2 + seed;
-    double r[2];
-    for (int k = 0; k < 2; ++k) {
-      uint64_t x = z + (uint64_t)k + 0x9E3779B97F4A7C15ull;
-      x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-      x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-      x = x ^ (x >> 31);
-      r[k] = (double)(x >> 11) * (1.0 / 9007199254740992.0) - 0.5;
-    }
-    q[i] = make_double2(sgn * r[0], sgn * r[1]);
-  }
 }
 
 // In-place basis rotation  V[:, 0..k) <- V[:, 0..m) * S  (S real m x k, column-major S[l + j*m]).
@@ -387,8 +363,7 @@ extern "C" {
 int hxv_eigh_lowest(hxv_handle* h, int32_t neigen, int32_t ncv, int32_t maxrestart, double tol, double* evals, void* d_evecs,
                     int32_t* nconv_out, int32_t* nmatvec_out) {
   if (!h || !evals || neigen < 1 || maxrestart < 0) return fail(HXV_ERR_ARG, "hxv_eigh_lowest: bad argument");
-  if (h->host.nranks != 1 && !comm_ready(h))
-    return fail(HXV_ERR_STATE, "hxv_eigh_lowest on a split sector needs the communicator: call hxv_comm_init after opening the sector");
+  if (int rcc = need_comm(h, "hxv_eigh_lowest")) return rcc;
   HIPCHK(hipSetDevice(h->device));  // (before the first collective: thread ranks on several GPUs each have their own current device)
   const int64_t dim = h->host.dim;
   if (ncv <= 0) ncv = 10 * neigen;  // the reference's default: lanc_ncv_factor=10, lanc_ncv_add=0 (ED_INPUT_VARS.f90:174-175)
@@ -405,7 +380,7 @@ int hxv_eigh_lowest(hxv_handle* h, int32_t neigen, int32_t ncv, int32_t maxresta
   HIPCHK(hipSetDevice(h->device));
   // REAL-vector mode (H real, our own real start vector): the basis holds double[DimDw][pitch_real]; every kernel below
   // is elementwise with real coefficients, so it runs unchanged on the vectors viewed as n double2 elements.
-  const bool real = h->real_vectors && !real_mode_blocker(h);
+  const bool real = want_real(h);
   h->last_real = real ? 1 : 0;
   const int64_t nc = (int64_t)h->host.pitch * h->host.qdw;  // this rank's padded complex slab (pads are zero and stay zero)
   const int64_t n = real ? (int64_t)pitch_real_of(h) * h->host.qdw / 2 : nc;
@@ -633,11 +608,12 @@ int hxv_eigh_lowest(hxv_handle* h, int32_t neigen, int32_t ncv, int32_t maxresta
     T.assign((size_t)ma * ma, 0.0);
     auto t_at = [&](int i, int j) -> double& { return T[i + (size_t)j * ma]; };
     for (int i = nlock; i <= m; ++i) nv[i] = 1.0;  // (the locked vectors are unit vectors: every round ends with a rotation)
-    // start vector (deterministic hash of the global index; a different seed per round), made orthogonal to the locked set
+    // start vector (the single-vector Lanczos drivers' deterministic hash of the global index; a different seed per round), made orthogonal
+    // to the locked set
     if (real)
       launch_init_real(h, (double*)av(0), seed, st);
     else
-      hipLaunchKernelGGL(tr_init, dim3(g), dim3(256), 0, st, n, av(0), seed, h->host.dimup, h->host.pitch, h->host.dw0, h->dev.up_iperm, h->dev.up_sign);
+      launch_init(h, av(0), seed, st);
     double nrm2 = 0.0;
     if (nlock > 0) {
       for (int pass = 0; pass < 2; ++pass) {  // V[nlock] plays w: project the locked vectors out, twice

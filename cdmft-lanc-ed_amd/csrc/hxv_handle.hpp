@@ -16,6 +16,19 @@ struct hxv_handle;
 namespace hxv {
 int fail(int code, const std::string& msg);  // records the message hxv_last_error() returns; returns code
 constexpr int RED_BLOCKS = 1024;             // workgroups of the grid-stride reduction kernels
+// slots of the Lanczos scalars in device memory: hxv_handle::d_scalars [8]; the paired driver has a block of 2*LZ_PAIR of its own, the second
+// component's scalars LZ_PAIR behind the first one's
+enum LzSlot : int {
+  LZ_ALPHA = 0,
+  LZ_BETA = 1,
+  LZ_S = 2,        // s = 1/beta_k: the stored vector times s is the unit Lanczos vector
+  LZ_C = 3,        // c = beta_k/beta_{k-1}: coefficient of the previous stored vector
+  LZ_ALPHA_S = 4,  // alpha*s: coefficient of the stored vector in the subtract-and-norm pass
+  LZ_TMP = 5,      // norms and checks outside the recurrence
+  LZ_STEP = 6,     // step counter of the device-only iterations (lz_next)
+  LZ_AGREE = 7,    // comm_agree's status all-reduce (hxv_comm.cpp)
+  LZ_PAIR = 8
+};
 // vector-sized device buffers go through the engine's cache (hxv_pool.cpp): a fresh hipMalloc costs ~25 ms per GB here
 hipError_t pool_alloc(int device, size_t bytes, void** out);
 void pool_free(int device, void* ptr);
@@ -26,6 +39,7 @@ bool comm_in_gather(const hxv_handle* h, const void* p);  // p lies in one of th
 int comm_allreduce_sum(hxv_handle* h, double* d_buf, size_t count, hipStream_t st);  // no-op without a communicator
 int comm_sendrecv_cols(hxv_handle* h, const void* send, const int64_t* send_ptr, void* recv, const int64_t* recv_ptr, size_t col_bytes, hipStream_t st);
 int comm_agree(hxv_handle* h, int rc_local);  // collective: non-zero on every rank if any rank passes non-zero (no-op without a communicator)
+int need_comm(const hxv_handle* h, const char* who);  // HXV_ERR_STATE ("<who> on a split sector needs the communicator...") for a split sector without one
 // this rank's slab -> d_full, every rank's slab at column slot rank*cmax (the padded all-gather layout, whatever exchange mode h uses)
 int comm_allgather_slab(hxv_handle* h, const double2* d_v_local, double2* d_full, hipStream_t st);
 // (H v)|slab from this rank's slab: exchange + product; `ep`: optional Lanczos epilogue of pass A (its partial sums are this rank's share)
@@ -34,13 +48,15 @@ int apply_slab_real(hxv_handle* h, const double* d_v_local, double* d_hv_local, 
 void comm_release(hxv_handle* h);
 // REAL-vector mode helpers shared by the Lanczos drivers (hxv_capi.hip / hxv_lanczos.hip)
 const char* real_mode_blocker(const hxv_handle* h);  // nullptr when real vectors can be used with this handle
+bool want_real(const hxv_handle* h);                 // option real_vectors is on and nothing blocks it
 int pitch_real_of(const hxv_handle* h);
 // layout conversions between complex [DimDw][pitch] and real [DimDw][pitch_real] device vectors (pads written as zero)
 void launch_to_real(const hxv_handle* h, const double2* src, double* dst, hipStream_t st);
 void launch_to_complex(const hxv_handle* h, const double* src, double2* dst, hipStream_t st);
-// deterministic start vector, real part of the complex one (imaginary part dropped)
+// deterministic start vector of this rank's slab (a hash of the global reference index) / its real part
+void launch_init(const hxv_handle* h, double2* q, uint64_t seed, hipStream_t st);
 void launch_init_real(const hxv_handle* h, double* q, uint64_t seed, hipStream_t st);
-// one Lanczos step on normalised vectors through the fused product (hxv_lanczos.hip): w = H q - beta*qm, alpha = <q,w>, w -= alpha*q, |w|
+// split sector: the slab's home in the three gather buffers, for the three Lanczos vectors (HXV_ERR_HIP: no memory for them)
 int comm_lz_homes(hxv_handle* h, bool real, double2* out[3]);
 // this rank's slab between a HOST array in the reference's layout (contiguous columns of DimUp, the reference's row order) and a DEVICE vector
 // (columns padded to pitch, rows in the device row order with the basis signs of SectorHost::up_perm).  Synchronous: returns when the copy is
@@ -114,6 +130,8 @@ struct SectorImage {
 std::string sector_cache_key(const hxv_model& m, int nup, int ndw, int rank, int nranks, int device, int exchange);
 std::shared_ptr<SectorImage> sector_cache_find(const std::string& key);
 void sector_cache_insert(const std::shared_ptr<SectorImage>& im);
+// the fused Lanczos step (hxv_lanczos.hip) for callers that keep their own basis (hxv_eigh_lowest); _available: may this handle use the
+// fused product at all (the device drivers ask the same question)
 bool lanczos_local_step_available(const hxv_handle* h);
 int lanczos_local_step(hxv_handle* h, bool real, const double2* q, double sq, const double2* qm, double sqm, double beta, double2* w,
                        bool sub_alpha, double* alpha, double* nrm_w);

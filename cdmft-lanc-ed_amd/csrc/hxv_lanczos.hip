@@ -1,6 +1,8 @@
 // Device Lanczos behind the C-ABI (include/hxv.h): the single-vector recurrences with the SciFortran call shapes
-// (sp_lanc_tridiag, sp_lanc_eigh; ED_GF_NORMAL.f90:215-220, ED_DIAG.f90:176-184), the Green's-function start vectors
-// (c / c^dagger on the ground state, ED_GF_NORMAL.f90:180-199) and the iteration timer of bench.py.
+// (sp_lanc_tridiag, sp_lanc_eigh; ED_GF_NORMAL.f90:215-220, ED_DIAG.f90:176-184), the paired tridiagonalisation, the Green's-function
+// start vectors (c / c^dagger on the ground state, ED_GF_NORMAL.f90:180-199) and the iteration timer of bench.py.
+// Every driver -- and the local step hxv_eigh_lowest borrows -- takes its fused iteration from ONE function, fused_step_enqueue; the drivers
+// differ in who provides s and c (a host upload, or lz_next on the device), in whether there is a previous vector, and in what they read back.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -13,6 +15,19 @@ using namespace hxv;
 // Device Lanczos
 // ===========================================================================================
 namespace {
+
+// sum of `acc` over the 256 threads of a workgroup (every thread gets it): the LDS tree the one-accumulator reductions end with.  The kernels
+// with two and three accumulators keep their trees written out (one barrier per level for all of them).
+__device__ __forceinline__ double block_sum(double acc) {
+  __shared__ double red[256];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  return red[0];
+}
 
 // w -= b*qm ; partial sums of Re<q,w>
 __global__ void __launch_bounds__(256) lz_sub_dot(int64_t n, double2* __restrict__ w, const double2* __restrict__ qm,
@@ -31,14 +46,8 @@ __global__ void __launch_bounds__(256) lz_sub_dot(int64_t n, double2* __restrict
     double2 y = q[i];
     acc += y.x * x.x + y.y * x.y;
   }
-  __shared__ double red[256];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  const double sum = block_sum(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 // w -= a*q ; partial sums of |w|^2
@@ -59,14 +68,8 @@ __global__ void __launch_bounds__(256) lz_sub_nrm(int64_t n, double2* __restrict
       acc = acc + fma(x.y, x.y, t);
     }
   }
-  __shared__ double red[256];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  const double sum = block_sum(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 // PAIRED vectors (real part = vector a, imaginary part = vector b): w.re -= a_a*q.re, w.im -= a_b*q.im; partial sums of
@@ -149,28 +152,16 @@ __global__ void __launch_bounds__(256) lz_nrm(int64_t n, const double2* __restri
       acc = acc + fma(a.y, a.y, t);
     }
   }
-  __shared__ double red[256];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  const double sum = block_sum(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 // scal[io] = op(sum partial[0..np))   op: 0 identity, 1 sqrt
 __global__ void __launch_bounds__(256) lz_final(const double* __restrict__ partial, int np, double* __restrict__ scal, int io, int op) {
-  __shared__ double red[256];
   double acc = 0.0;
   for (int i = threadIdx.x; i < np; i += 256) acc += partial[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) scal[io] = op ? sqrt(red[0]) : red[0];
+  const double sum = block_sum(acc);
+  if (threadIdx.x == 0) scal[io] = op ? sqrt(sum) : sum;
 }
 
 // q = w / scal[ib]
@@ -239,14 +230,8 @@ __global__ void __launch_bounds__(256) lz_to_real(int dimup, int dimdw, int pc, 
     }
     if (dst) dst[i] = x;
   }
-  __shared__ double red[256];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && partial) partial[blockIdx.x] = red[0];
+  const double sum = block_sum(acc);
+  if (threadIdx.x == 0 && partial) partial[blockIdx.x] = sum;
 }
 
 // complex [DimDw][pc] <- real [DimDw][pr]; pads zero
@@ -335,71 +320,158 @@ bool tridiag_ql(int n, std::vector<double>& d, std::vector<double>& e, std::vect
   return true;
 }
 
-struct LzBuf {
-  double2 *q, *qm, *w;
-};
-
 // scal[i] = scal[a] * scal[b]
 __global__ void lz_mul(double* scal, int i, int a, int b) { scal[i] = scal[a] * scal[b]; }
 // scal[i] = sqrt(scal[i])   (split sector: the square root comes after the all-reduce of the partial sums of squares)
 __global__ void lz_sqrt(double* scal, int i) { scal[i] = sqrt(scal[i]); }
 
 // sum (op 0) or 2-norm (op 1) of the per-workgroup partials into scal[io]; on a split sector the sums of all ranks are added
-int reduce_scalar(hxv_handle* h, const double* partial, int np, int io, int op) {
+int reduce_scalar(hxv_handle* h, const double* partial, int np, int io, int op, double* scal = nullptr) {
+  if (!scal) scal = h->d_scalars;
   const bool dist = comm_ready(h);
-  hipLaunchKernelGGL(lz_final, dim3(1), dim3(256), 0, h->stream, partial, np, h->d_scalars, io, dist ? 0 : op);
+  hipLaunchKernelGGL(lz_final, dim3(1), dim3(256), 0, h->stream, partial, np, scal, io, dist ? 0 : op);
   if (dist) {
-    int rc = comm_allreduce_sum(h, h->d_scalars + io, 1, h->stream);
+    int rc = comm_allreduce_sum(h, scal + io, 1, h->stream);
     if (rc) return rc;
-    if (op) hipLaunchKernelGGL(lz_sqrt, dim3(1), dim3(1), 0, h->stream, h->d_scalars, io);
+    if (op) hipLaunchKernelGGL(lz_sqrt, dim3(1), dim3(1), 0, h->stream, scal, io);
   }
   return HXV_OK;
 }
 
-// End of one fused iteration without the host: record alpha_k = scal[0], beta_{k+1} = scal[1] at the device-side step
-// counter scal[6], and prepare the next iteration's scalars  s = 1/beta_{k+1} (scal[2]),  c = s_old/s = beta_{k+1}/beta_k (scal[3]).
-__global__ void lz_next(double* scal, double* alpha_out, double* beta_out, int nmax) {
-  const int k = (int)scal[6];
-  if (k < nmax) {
-    alpha_out[k] = scal[0];
-    if (k + 1 < nmax) beta_out[k + 1] = scal[1];
-  }
-  // (the same operations, in the same order, as LzRunner::advance() + step() on the host: bit-identical recurrences)
-  const double beta_prev = 1.0 / scal[2], s_new = 1.0 / scal[1];
-  scal[2] = s_new;
-  scal[3] = 1.0 / (s_new * beta_prev);
-  scal[6] = (double)(k + 1);
+// scal[slot] = |x|^2 (op 0) or |x| (op 1) of the n double2 elements of x, over all ranks of a split sector
+int enqueue_norm(hxv_handle* h, const double2* x, int64_t n, int slot, int op) {
+  const int g = grid_for(n);
+  hipLaunchKernelGGL(lz_nrm, dim3(g), dim3(256), 0, h->stream, n, x, h->d_partials + RED_BLOCKS);
+  return reduce_scalar(h, h->d_partials + RED_BLOCKS, g, slot, op);
 }
+// q = w / |w|   (q may be w); the norm stays in scal[slot]
+int enqueue_normalise(hxv_handle* h, double2* q, const double2* w, int64_t n, int slot) {
+  int rc = enqueue_norm(h, w, n, slot, 1);
+  if (rc) return rc;
+  hipLaunchKernelGGL(lz_scale, dim3(grid_for(n)), dim3(256), 0, h->stream, n, q, w, h->d_scalars, slot);
+  return HXV_OK;
+}
+
+// double2 elements of one Lanczos vector of this rank (local slab: qdw == DimDw on an unsplit sector).  REAL-vector mode: the buffers hold
+// double[DimDw][pitch_real]; every streaming kernel here is elementwise with real scalars, so it runs unchanged on that buffer viewed as double2
+int64_t lz_len(const hxv_handle* h, bool real) {
+  return real ? (int64_t)pitch_real_of(h) * h->host.qdw / 2 : (int64_t)h->host.pitch * h->host.qdw;
+}
+// workgroups of pass A = partial sums its epilogue leaves (a rank without columns launches nothing: one zero stands in)
+int64_t lz_pass_a_workgroups(const hxv_handle* h, bool real) {
+  return std::max<int64_t>(1, tiled_pass_up_workgroups(h->dev, h->plan, real, dw_part_in_pieces(h)));
+}
+// room for n partial sums of the epilogue
+int ensure_lz_partial(hxv_handle* h, int64_t n) {
+  if (n <= h->lz_partial_n) return HXV_OK;
+  if (h->d_lz_partial) (void)hipFree(h->d_lz_partial);
+  h->d_lz_partial = nullptr;
+  h->lz_partial_n = 0;
+  HIPCHK(hipMalloc((void**)&h->d_lz_partial, (size_t)n * sizeof(double)));
+  HIPCHK(hipMemsetAsync(h->d_lz_partial, 0, (size_t)n * sizeof(double), h->stream));  // (a rank without columns launches nothing)
+  h->lz_partial_n = n;
+  return HXV_OK;
+}
+
+// THE fused Lanczos step, enqueued on the handle's stream; every device driver runs this one sequence, so what they promise each other bit
+// for bit (paired = two single runs, captured = host-stepped, local step = normalised step) holds by construction.  With the stored vectors
+// q = X_k, qm = X_{k-1} (null: no previous vector, c is not read) and s = scal[LZ_S], c = scal[LZ_C] ALREADY in device memory -- uploaded by
+// the caller or left there by lz_next -- pass A's epilogue stores  w = s*H q - c*qm  and the partial sums of  alpha = <s q, w>  -> scal[LZ_ALPHA];
+// with sub_alpha one more pass subtracts (alpha*s) q and reduces  beta = |w|  -> scal[LZ_BETA].  On a split sector alpha and beta are summed
+// over the ranks.  pair: Re and Im of the vectors are two independent real recurrences, the second one's scalars LZ_PAIR behind the first's.
+// Nothing here allocates, copies or synchronises once the buffers have their size, so the sequence can be captured into a hipGraph: the
+// product's scratch and the partial sums grow on the first call (iteration 0 always runs uncaptured), and apply_slab's event marks are only
+// armed inside hxv_time_apply_slab.
+int fused_step_enqueue(hxv_handle* h, bool real, const double2* q, const double2* qm, double2* w, double* scal, bool pair, bool sub_alpha = true) {
+  const int64_t n2 = lz_len(h, real), nwg = lz_pass_a_workgroups(h, real);
+  const int g = grid_for(n2), nc = pair ? 2 : 1;
+  int rc = ensure_lz_partial(h, nc * nwg);
+  if (rc) return rc;
+  LzEpilogue ep;
+  ep.xm = qm;
+  ep.scal = scal;
+  ep.i_s = LZ_S;
+  ep.i_c = LZ_C;
+  ep.partial = h->d_lz_partial;
+  if (pair) {
+    ep.pair = 1;
+    ep.i_s2 = LZ_PAIR + LZ_S;
+    ep.i_c2 = LZ_PAIR + LZ_C;
+    ep.partial2 = h->d_lz_partial + nwg;
+  }
+  // (apply_slab = exchange + product on a split sector, the plain product otherwise)
+  rc = real ? apply_slab_real(h, (const double*)q, (double*)w, h->stream, &ep) : apply_slab(h, q, w, h->stream, &ep);
+  for (int c = 0; c < nc && !rc; ++c) rc = reduce_scalar(h, h->d_lz_partial + c * nwg, (int)nwg, c * LZ_PAIR + LZ_ALPHA, 0, scal);
+  if (rc || !sub_alpha) return rc;
+  for (int c = 0; c < nc; ++c)  // alpha*s: the coefficient of the STORED q
+    hipLaunchKernelGGL(lz_mul, dim3(1), dim3(1), 0, h->stream, scal, c * LZ_PAIR + LZ_ALPHA_S, c * LZ_PAIR + LZ_ALPHA, c * LZ_PAIR + LZ_S);
+  double* pb[2] = {h->d_partials + RED_BLOCKS, h->d_partials};
+  if (pair)
+    hipLaunchKernelGGL(lz_sub_nrm_pair, dim3(g), dim3(256), 0, h->stream, n2, w, q, scal, LZ_ALPHA_S, LZ_PAIR + LZ_ALPHA_S, pb[0], pb[1]);
+  else
+    hipLaunchKernelGGL(lz_sub_nrm, dim3(g), dim3(256), 0, h->stream, n2, w, q, scal, LZ_ALPHA_S, pb[0]);
+  for (int c = 0; c < nc && !rc; ++c) rc = reduce_scalar(h, pb[c], g, c * LZ_PAIR + LZ_BETA, 1, scal);
+  return rc;
+}
+
+// The host's copy of one component's scale factors in the fused recurrence: the stored vector X_k times s_cur = 1/beta_k is the unit Lanczos
+// vector, beta_prev = beta_{k-1} (the start vector's norm is carried as beta_0).
+struct LzScale {
+  double s_cur = 1.0, beta_prev = 1.0;
+  void begin(double nrm) {
+    s_cur = 1.0 / nrm;
+    beta_prev = nrm;
+  }
+  double c() const { return 1.0 / (s_cur * beta_prev); }  // beta_k / beta_{k-1}: what LZ_C holds from the second step on
+  // after a step that returned beta_{k+1}  (lz_next does the same operations, in the same order, on the device: bit-identical recurrences)
+  void next(double beta) {
+    beta_prev = 1.0 / s_cur;
+    s_cur = 1.0 / beta;
+  }
+};
+
+// End of one fused iteration without the host: record alpha_k, beta_{k+1} at the device-side step counter scal[LZ_STEP], and prepare the
+// next iteration's scalars  s = 1/beta_{k+1},  c = s_old/s = beta_{k+1}/beta_k.
+__global__ void lz_next(double* scal, double* alpha_out, double* beta_out, int nmax) {
+  const int k = (int)scal[LZ_STEP];
+  if (k < nmax) {
+    alpha_out[k] = scal[LZ_ALPHA];
+    if (k + 1 < nmax) beta_out[k + 1] = scal[LZ_BETA];
+  }
+  // (the same operations, in the same order, as LzScale::next() + c() on the host: bit-identical recurrences)
+  const double beta_prev = 1.0 / scal[LZ_S], s_new = 1.0 / scal[LZ_BETA];
+  scal[LZ_S] = s_new;
+  scal[LZ_C] = 1.0 / (s_new * beta_prev);
+  scal[LZ_STEP] = (double)(k + 1);
+}
+
+struct LzBuf {
+  double2 *q, *qm, *w;
+};
 
 // Lanczos recurrence on device.  Two implementations of one step:
 //  * plain : w = H q (any kernel), then lz_sub_dot / lz_sub_nrm / lz_scale on normalised vectors;
-//  * fused : vectors are kept UNNORMALISED (q_k = s*X, s = 1/beta_k); pass A's epilogue produces
-//            w = s*H X - c*Xm and the partial sums of alpha, one more pass subtracts alpha*q and reduces beta.
+//  * fused : vectors are kept UNNORMALISED (q_k = s*X, s = 1/beta_k) and go through fused_step_enqueue.
 //            144 B/state per iteration instead of 224.
 struct LzRunner {
   hxv_handle* h;
   LzBuf b;
   bool fused;
-  bool real;            // REAL-vector mode: the buffers hold double[DimDw][pitch_real]; every streaming kernel below is
-                        // elementwise with real scalars, so it runs unchanged on the buffer viewed as n2 double2 elements
+  bool real;            // REAL-vector mode (see lz_len)
   int64_t n2;           // double2 elements of one vector
   bool first = true;
-  double s_cur = 1.0;   // q = s_cur * b.q (fused) ; 1 (plain)
-  double beta_prev = 1.0;
+  LzScale sc;           // q = sc.s_cur * b.q (fused) ; 1 (plain)
+  double last_beta = 0.0;
 
-  LzRunner(hxv_handle* hh, double2* x, double2* xm, double2* w, bool real_vec = false) : h(hh), b{x, xm, w}, real(real_vec) {
-    // (split sectors included: the epilogue's partial sums are this rank's share, alpha and beta are all-reduced)
-    fused = hh->kernel == 1 && hh->plan.usable && (!hh->dev.nd.active || nd_folds(hh->dev)) && hh->plan.opt.passes == 3 && hh->plan.opt.debug == 0 && hh->lz_fused;
-    // (local slab: qdw == DimDw on an unsplit sector)
-    n2 = real ? (int64_t)pitch_real_of(hh) * hh->host.qdw / 2 : (int64_t)hh->host.pitch * hh->host.qdw;
+  LzRunner(hxv_handle* hh, double2* x, double2* xm, double2* w, bool real_vec = false)
+      : h(hh), b{x, xm, w}, fused(lanczos_local_step_available(hh)), real(real_vec), n2(lz_len(hh, real_vec)) {
     hh->last_real = real ? 1 : 0;
   }
 
   // b.q holds a vector of norm `nrm` (pass 1.0 if already normalised)
   int begin(double nrm) {
     first = true;
-    s_cur = 1.0 / nrm;
-    beta_prev = nrm;
+    sc.begin(nrm);
     if (!fused && nrm != 1.0) return fail(HXV_ERR_STATE, "plain Lanczos expects a normalised start vector");
     return HXV_OK;
   }
@@ -407,46 +479,24 @@ struct LzRunner {
   int step(double* alpha, double* beta) {
     const int64_t n = n2;
     const int g = grid_for(n);
+    int rc;
     if (!fused) {
       // (apply_slab = exchange + product on a split sector, the plain product otherwise)
-      int rc = real ? apply_slab_real(h, (const double*)b.q, (double*)b.w, h->stream) : apply_slab(h, b.q, b.w, h->stream);
+      rc = real ? apply_slab_real(h, (const double*)b.q, (double*)b.w, h->stream) : apply_slab(h, b.q, b.w, h->stream);
       if (rc) return rc;
-      hipLaunchKernelGGL(lz_sub_dot, dim3(g), dim3(256), 0, h->stream, n, b.w, b.qm, b.q, h->d_scalars, first ? -1 : 2, h->d_partials);
-      rc = reduce_scalar(h, h->d_partials, g, 0, 0);
+      hipLaunchKernelGGL(lz_sub_dot, dim3(g), dim3(256), 0, h->stream, n, b.w, b.qm, b.q, h->d_scalars, first ? -1 : (int)LZ_S, h->d_partials);
+      rc = reduce_scalar(h, h->d_partials, g, LZ_ALPHA, 0);
       if (rc) return rc;
-      hipLaunchKernelGGL(lz_sub_nrm, dim3(g), dim3(256), 0, h->stream, n, b.w, b.q, h->d_scalars, 0, h->d_partials + RED_BLOCKS);
-      rc = reduce_scalar(h, h->d_partials + RED_BLOCKS, g, 1, 1);
-      if (rc) return rc;
+      hipLaunchKernelGGL(lz_sub_nrm, dim3(g), dim3(256), 0, h->stream, n, b.w, b.q, h->d_scalars, LZ_ALPHA, h->d_partials + RED_BLOCKS);
+      rc = reduce_scalar(h, h->d_partials + RED_BLOCKS, g, LZ_BETA, 1);
     } else {
-      const int64_t nwg = std::max<int64_t>(1, tiled_pass_up_workgroups(h->dev, h->plan, real, dw_part_in_pieces(h)));
-      if (nwg > h->lz_partial_n) {
-        if (h->d_lz_partial) (void)hipFree(h->d_lz_partial);
-        h->d_lz_partial = nullptr;
-        h->lz_partial_n = 0;
-        HIPCHK(hipMalloc((void**)&h->d_lz_partial, (size_t)nwg * sizeof(double)));
-        HIPCHK(hipMemsetAsync(h->d_lz_partial, 0, (size_t)nwg * sizeof(double), h->stream));  // (a rank without columns launches nothing)
-        h->lz_partial_n = nwg;
-      }
-      // scal[2] = s, scal[3] = c = beta_k / beta_{k-1}
-      const double sc[2] = {s_cur, first ? 0.0 : 1.0 / (s_cur * beta_prev)};
-      HIPCHK(hipMemcpyAsync(h->d_scalars + 2, sc, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      LzEpilogue ep;
-      ep.xm = first ? nullptr : b.qm;
-      ep.scal = h->d_scalars;
-      ep.i_s = 2;
-      ep.i_c = 3;
-      ep.partial = h->d_lz_partial;
-      int rc = real ? apply_slab_real(h, (const double*)b.q, (double*)b.w, h->stream, &ep) : apply_slab(h, b.q, b.w, h->stream, &ep);
-      if (rc) return rc;
-      rc = reduce_scalar(h, h->d_lz_partial, (int)nwg, 0, 0);  // alpha: summed over the ranks of a split sector
-      if (rc) return rc;
-      hipLaunchKernelGGL(lz_mul, dim3(1), dim3(1), 0, h->stream, h->d_scalars, 4, 0, 2);
-      hipLaunchKernelGGL(lz_sub_nrm, dim3(g), dim3(256), 0, h->stream, n, b.w, b.q, h->d_scalars, 4, h->d_partials + RED_BLOCKS);
-      rc = reduce_scalar(h, h->d_partials + RED_BLOCKS, g, 1, 1);
-      if (rc) return rc;
+      const double up[2] = {sc.s_cur, first ? 0.0 : sc.c()};  // -> LZ_S, LZ_C
+      HIPCHK(hipMemcpyAsync(h->d_scalars + LZ_S, up, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      rc = fused_step_enqueue(h, real, b.q, first ? nullptr : b.qm, b.w, h->d_scalars, false);
     }
+    if (rc) return rc;
     double host[2];
-    HIPCHK(hipMemcpyAsync(host, h->d_scalars, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(host, h->d_scalars + LZ_ALPHA, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *alpha = host[0];
     *beta = host[1];
@@ -454,48 +504,31 @@ struct LzRunner {
     return HXV_OK;
   }
 
-  // One fused iteration enqueued with NO host involvement: s and c are read from scal[2], scal[3] (left there by the
-  // previous lz_next), alpha/beta go to device arrays.  q, qm, w are explicit so that a rotation cycle can be captured.
-  int enqueue_device_iteration(double2* q, double2* qm, double2* w, double* d_alpha, double* d_beta, int nmax) {
-    const int g = grid_for(n2);
-    const int64_t nwg = tiled_pass_up_workgroups(h->dev, h->plan, real, dw_part_in_pieces(h));
-    LzEpilogue ep;
-    ep.xm = qm;
-    ep.scal = h->d_scalars;
-    ep.i_s = 2;
-    ep.i_c = 3;
-    ep.partial = h->d_lz_partial;
-    hipError_t e;
-    if (real) {
-      DevSector d = h->dev;
-      d.pitch = pitch_real_of(h);
-      e = launch_hxv_tiled_real(d, h->plan, (const double*)q, (double*)h->d_wt, (double*)w, h->stream, &ep);
-    } else {
-      e = launch_hxv_tiled(h->dev, h->plan, q, h->d_wt, w, h->stream, &ep);
-    }
-    if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    h->n_apply++;
-    hipLaunchKernelGGL(lz_final, dim3(1), dim3(256), 0, h->stream, h->d_lz_partial, (int)nwg, h->d_scalars, 0, 0);
-    hipLaunchKernelGGL(lz_mul, dim3(1), dim3(1), 0, h->stream, h->d_scalars, 4, 0, 2);
-    hipLaunchKernelGGL(lz_sub_nrm, dim3(g), dim3(256), 0, h->stream, n2, w, q, h->d_scalars, 4, h->d_partials + RED_BLOCKS);
-    hipLaunchKernelGGL(lz_final, dim3(1), dim3(256), 0, h->stream, h->d_partials + RED_BLOCKS, g, h->d_scalars, 1, 1);
-    hipLaunchKernelGGL(lz_next, dim3(1), dim3(1), 0, h->stream, h->d_scalars, d_alpha, d_beta, nmax);
-    return HXV_OK;
+  // Hand-over from iteration 0 (done by step(), which returned `beta`) to the device-only iterations: the scalars of iteration 1 and the
+  // step counter go to device memory, where lz_next keeps them from then on.
+  hipError_t begin_device_iterations(double beta) {
+    const double s1 = 1.0 / beta, bprev = 1.0 / sc.s_cur;
+    const double init[2] = {s1, 1.0 / (s1 * bprev)};   // s_1 = 1/beta_1 ; c_1 = beta_1/beta_0, rounded like LzScale::next() + c()
+    const double one = 1.0;
+    hipError_t e = hipMemcpyAsync(h->d_scalars + LZ_S, init, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->d_scalars + LZ_STEP, &one, sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (init and one are read by asynchronous copies)
+    return e;
   }
 
-  // Iterations 1..nmax-1 of a fixed-length run on the device alone (iteration 0 was done by step(); scal[2], scal[3],
-  // scal[6] are set): the three-iteration pointer-rotation cycle is captured ONCE into a hipGraph and replayed, so a
-  // small sector pays one graph launch per three iterations instead of ~9 kernel launches, two copies and a
+  // Iterations 1..nmax-1 of a fixed-length run on the device alone (after begin_device_iterations): each one is the fused step on the
+  // scalars lz_next left, then lz_next; alpha/beta go to device arrays.  The three-iteration pointer-rotation cycle is captured ONCE into a
+  // hipGraph and replayed, so a small sector pays one graph launch per three iterations instead of ~9 kernel launches, two copies and a
   // synchronisation per iteration.  Leaves b.q/b.qm/b.w as after the last iteration.
   int run_device_iterations(int nmax, double* d_alpha, double* d_beta, bool use_graph) {
     double2* buf[3] = {b.q, b.w, b.qm};  // iteration k uses q = buf[k%3] (k counted from 1: q = former w), w = buf[(k+1)%3], qm = buf[(k+2)%3]
     // after step() of iteration 0 and before any rotation: X_1 = b.w, X_0 = b.q, free = b.qm
     int k = 1;
     auto one = [&](int kk) -> int {
-      double2* q = buf[kk % 3];
-      double2* w = buf[(kk + 1) % 3];
-      double2* qm = buf[(kk + 2) % 3];
-      return enqueue_device_iteration(q, qm, w, d_alpha, d_beta, nmax);
+      int rc = fused_step_enqueue(h, real, buf[kk % 3], buf[(kk + 2) % 3], buf[(kk + 1) % 3], h->d_scalars, false);
+      if (rc) return rc;
+      hipLaunchKernelGGL(lz_next, dim3(1), dim3(1), 0, h->stream, h->d_scalars, d_alpha, d_beta, nmax);
+      return HXV_OK;
     };
     const int cycles = use_graph ? (nmax - 1) / 3 : 0;
     if (cycles >= 2) {
@@ -539,36 +572,30 @@ struct LzRunner {
   int advance() {
     const int64_t n = n2;
     if (!fused) {
-      HIPCHK(hipMemcpyAsync(h->d_scalars + 2, h->d_scalars + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(h->d_scalars + LZ_S, h->d_scalars + LZ_BETA, sizeof(double), hipMemcpyDeviceToDevice, h->stream));  // (plain: LZ_S holds beta_k)
       std::swap(b.q, b.qm);
-      hipLaunchKernelGGL(lz_scale, dim3(grid_for(n)), dim3(256), 0, h->stream, n, b.q, b.w, h->d_scalars, 2);
+      hipLaunchKernelGGL(lz_scale, dim3(grid_for(n)), dim3(256), 0, h->stream, n, b.q, b.w, h->d_scalars, LZ_S);
     } else {
       double2* old_m = b.qm;
       b.qm = b.q;      // X_{k-1}
       b.q = b.w;       // X_k = unnormalised residual
       b.w = old_m;
-      beta_prev = 1.0 / s_cur;   // beta_k
-      s_cur = 1.0 / last_beta;   // 1/beta_{k+1}
+      sc.next(last_beta);
     }
     first = false;
     return HXV_OK;
   }
 
-  double last_beta = 0.0;
   // current normalised Lanczos vector = scale() * vec()
   const double2* vec() const { return b.q; }
-  double scale() const { return fused ? s_cur : 1.0; }
+  double scale() const { return fused ? sc.s_cur : 1.0; }
 };
-
-// may this Lanczos run use real vectors?  (d_vin: optional complex start vector that must then be purely real)
-bool want_real(hxv_handle* h) { return h->real_vectors && !real_mode_blocker(h); }
 
 // the three work vectors of the single-vector Lanczos; `real` = layout of the coming run.  The pad rows of the two
 // layouts sit at different places and must be zero (the reductions run over the padded arrays, the products never
 // write pads), so the buffers are cleared whenever the layout changes.
 int ensure_lz(hxv_handle* h, bool real) {
-  if (h->host.nranks != 1 && !comm_ready(h))
-    return fail(HXV_ERR_STATE, "device Lanczos on a split sector needs the communicator: call hxv_comm_init after opening the sector");
+  if (int rcc = need_comm(h, "device Lanczos")) return rcc;
   HIPCHK(hipSetDevice(h->device));
   const size_t bytes = (size_t)h->host.pitch * std::max(h->host.qdw, 1) * sizeof(double2);
   if (comm_ready(h) && h->host.nranks > 1 && h->lz_inplace && h->host.exchange != 2) {
@@ -633,56 +660,40 @@ void launch_to_complex(const hxv_handle* h, const double* src, double2* dst, hip
   hipLaunchKernelGGL(lz_to_complex, dim3(grid_for((int64_t)h->host.pitch * h->host.qdw)), dim3(256), 0, st, h->host.dimup, h->host.qdw,
                      h->host.pitch, pitch_real_of(h), src, dst);
 }
-// One Lanczos step on NORMALISED vectors for callers that keep their own basis (hxv_eigh_lowest): w = H q - beta*qm through
-// pass A's epilogue (qm may be null), alpha = <q,w> from its partial sums, then w -= alpha*q and |w|.  False if the fused
-// product does not apply to this handle (the caller then measures the two projections itself).
+// may a Lanczos run on this handle use real vectors?  (a start vector the caller brings must be purely real as well)
+bool want_real(const hxv_handle* h) { return h->real_vectors && !real_mode_blocker(h); }
+int need_comm(const hxv_handle* h, const char* who) {
+  if (h->host.nranks == 1 || comm_ready(h)) return HXV_OK;
+  return fail(HXV_ERR_STATE, std::string(who) + " on a split sector needs the communicator: call hxv_comm_init after opening the sector");
+}
+// may this handle use the fused product?  (split sectors included: the epilogue's partial sums are this rank's share, alpha and beta are
+// all-reduced.)  When not, the drivers run the plain recurrence and hxv_eigh_lowest measures its two local projections itself.
 bool lanczos_local_step_available(const hxv_handle* h) {
   return h->kernel == 1 && h->plan.usable && (!h->dev.nd.active || nd_folds(h->dev)) && h->plan.opt.passes == 3 && h->plan.opt.debug == 0 && h->lz_fused;
 }
 
-// One Lanczos step on an UNNORMALISED pair: q = sq * (unit q_j), qm = sqm * (unit q_{j-1}).  The product's epilogue stores
-//   w = H q / sq - (beta / sqm) qm   and reduces   alpha = <q / sq, w>;
-// with sub_alpha one more pass subtracts alpha (q / sq) and measures |w|, otherwise w is left as it is and *nrm_w is not set (the caller
-// subtracts alpha together with other projections).  Scale factors 1.0 reproduce the normalised step bit for bit.
+// The fused step for callers that keep their own basis (hxv_eigh_lowest), on an UNNORMALISED pair: q = sq * (unit q_j),
+// qm = sqm * (unit q_{j-1}), qm may be null.  The product's epilogue stores   w = H q / sq - (beta / sqm) qm   and reduces
+// alpha = <q / sq, w>;  with sub_alpha one more pass subtracts alpha (q / sq) and measures |w|, otherwise w is left as it is and *nrm_w is
+// not set (the caller subtracts alpha together with other projections).  Scale factors 1.0 give the step on normalised vectors.
 int lanczos_local_step(hxv_handle* h, bool real, const double2* q, double sq, const double2* qm, double sqm, double beta, double2* w,
                        bool sub_alpha, double* alpha, double* nrm_w) {
-  const int64_t n2 = real ? (int64_t)pitch_real_of(h) * h->host.qdw / 2 : (int64_t)h->host.pitch * h->host.qdw;
-  const int g = grid_for(n2);
-  const int64_t nwg = std::max<int64_t>(1, tiled_pass_up_workgroups(h->dev, h->plan, real, dw_part_in_pieces(h)));
-  if (nwg > h->lz_partial_n) {
-    if (h->d_lz_partial) (void)hipFree(h->d_lz_partial);
-    h->d_lz_partial = nullptr;
-    h->lz_partial_n = 0;
-    HIPCHK(hipMalloc((void**)&h->d_lz_partial, (size_t)nwg * sizeof(double)));
-    HIPCHK(hipMemsetAsync(h->d_lz_partial, 0, (size_t)nwg * sizeof(double), h->stream));
-    h->lz_partial_n = nwg;
-  }
-  const double sc[2] = {1.0 / sq, qm ? beta / sqm : 0.0};
-  HIPCHK(hipMemcpyAsync(h->d_scalars + 2, sc, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  LzEpilogue ep;
-  ep.xm = qm;
-  ep.scal = h->d_scalars;
-  ep.i_s = 2;
-  ep.i_c = 3;
-  ep.partial = h->d_lz_partial;
-  int rc = real ? apply_slab_real(h, (const double*)q, (double*)w, h->stream, &ep) : apply_slab(h, q, w, h->stream, &ep);
+  const double up[2] = {1.0 / sq, qm ? beta / sqm : 0.0};  // -> LZ_S, LZ_C
+  HIPCHK(hipMemcpyAsync(h->d_scalars + LZ_S, up, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  int rc = fused_step_enqueue(h, real, q, qm, w, h->d_scalars, false, sub_alpha);
   if (rc) return rc;
-  rc = reduce_scalar(h, h->d_lz_partial, (int)nwg, 0, 0);
-  if (rc) return rc;
-  if (sub_alpha) {
-    hipLaunchKernelGGL(lz_mul, dim3(1), dim3(1), 0, h->stream, h->d_scalars, 4, 0, 2);  // alpha / sq: the coefficient of the stored q
-    hipLaunchKernelGGL(lz_sub_nrm, dim3(g), dim3(256), 0, h->stream, n2, w, q, h->d_scalars, 4, h->d_partials + RED_BLOCKS);
-    rc = reduce_scalar(h, h->d_partials + RED_BLOCKS, g, 1, 1);
-    if (rc) return rc;
-  }
   double host[2] = {0.0, 0.0};
-  HIPCHK(hipMemcpyAsync(host, h->d_scalars, (sub_alpha ? 2 : 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(host, h->d_scalars + LZ_ALPHA, (sub_alpha ? 2 : 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   *alpha = host[0];
   if (sub_alpha && nrm_w) *nrm_w = host[1];
   return HXV_OK;
 }
 
+void launch_init(const hxv_handle* h, double2* q, uint64_t seed, hipStream_t st) {
+  const int64_t n = (int64_t)h->host.pitch * h->host.qdw;
+  hipLaunchKernelGGL(lz_init, dim3(grid_for(n)), dim3(256), 0, st, n, q, seed, h->host.dimup, h->host.pitch, h->host.dw0, h->dev.up_iperm, h->dev.up_sign);
+}
 void launch_init_real(const hxv_handle* h, double* q, uint64_t seed, hipStream_t st) {
   const int64_t n = (int64_t)pitch_real_of(h) * h->host.qdw;
   hipLaunchKernelGGL(lz_init_real, dim3(grid_for(n)), dim3(256), 0, st, n, q, seed, h->host.dimup, pitch_real_of(h), h->host.dw0, h->dev.up_iperm, h->dev.up_sign);
@@ -703,17 +714,16 @@ int hxv_lanczos_tridiag(hxv_handle* h, const void* d_vin, int32_t nlanc, double*
   // the whole recurrence stays real; alanc/blanc are the same numbers at half the bytes per pass
   bool real = want_real(h);
   int rc_pre = HXV_OK;
-  if (h->host.nranks != 1 && !comm_ready(h))
-    return fail(HXV_ERR_STATE, "device Lanczos on a split sector needs the communicator: call hxv_comm_init after opening the sector");
+  if (int rcc = need_comm(h, "device Lanczos")) return rcc;
   if (real) {  // sum of Im(vin)^2 over ALL ranks (dst = null: reduction only): every rank must take the same path
     const int pr = pitch_real_of(h);
     const int g = grid_for((int64_t)pr * h->host.qdw);
     hipLaunchKernelGGL(lz_to_real, dim3(g), dim3(256), 0, h->stream, h->host.dimup, h->host.qdw, h->host.pitch, pr,
                        (const double2*)d_vin, (double*)nullptr, h->d_partials);
     // (a rank that fails here must still meet its peers in the agreement below, not leave them there: ADVICE r4)
-    rc_pre = reduce_scalar(h, h->d_partials, g, 5, 0);
+    rc_pre = reduce_scalar(h, h->d_partials, g, LZ_TMP, 0);
     double im2 = 0.0;
-    if (!rc_pre && hipMemcpyAsync(&im2, h->d_scalars + 5, sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc_pre = fail(HXV_ERR_HIP, "hxv_lanczos_tridiag: reading the real-vector check failed");
+    if (!rc_pre && hipMemcpyAsync(&im2, h->d_scalars + LZ_TMP, sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc_pre = fail(HXV_ERR_HIP, "hxv_lanczos_tridiag: reading the real-vector check failed");
     if (!rc_pre && hipStreamSynchronize(h->stream) != hipSuccess) rc_pre = fail(HXV_ERR_HIP, "hxv_lanczos_tridiag: the real-vector check failed");
     real = im2 == 0.0;
   }
@@ -728,12 +738,10 @@ int hxv_lanczos_tridiag(hxv_handle* h, const void* d_vin, int32_t nlanc, double*
   // SciFortran's sp_lanc_tridiag normalises vin on its first iteration; the reference's call sites pass a normalised
   // vector already (ED_GF_NORMAL.f90:197-199).  Measure the (global) norm and normalise only when it is not 1.
   {
-    const int gq = grid_for(lz.n2);
-    hipLaunchKernelGGL(lz_nrm, dim3(gq), dim3(256), 0, h->stream, lz.n2, lz.b.q, h->d_partials + RED_BLOCKS);
-    rc = reduce_scalar(h, h->d_partials + RED_BLOCKS, gq, 5, 1);
+    rc = enqueue_norm(h, lz.b.q, lz.n2, LZ_TMP, 1);
     if (rc) return rc;
     double nrm = 0.0;
-    HIPCHK(hipMemcpyAsync(&nrm, h->d_scalars + 5, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&nrm, h->d_scalars + LZ_TMP, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (!(nrm > 0.0) || !std::isfinite(nrm)) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag: the start vector is zero or not finite");
     if (std::fabs(nrm - 1.0) <= 1e-14) {
@@ -741,7 +749,7 @@ int hxv_lanczos_tridiag(hxv_handle* h, const void* d_vin, int32_t nlanc, double*
     } else if (lz.fused) {
       rc = lz.begin(nrm);  // the fused recurrence carries the scale factor
     } else {
-      hipLaunchKernelGGL(lz_scale, dim3(gq), dim3(256), 0, h->stream, lz.n2, lz.b.q, lz.b.q, h->d_scalars, 5);
+      hipLaunchKernelGGL(lz_scale, dim3(grid_for(lz.n2)), dim3(256), 0, h->stream, lz.n2, lz.b.q, lz.b.q, h->d_scalars, LZ_TMP);
       rc = lz.begin(1.0);
     }
   }
@@ -766,13 +774,7 @@ int hxv_lanczos_tridiag(hxv_handle* h, const void* d_vin, int32_t nlanc, double*
       double* d_ab = nullptr;
       HIPCHK(hipMalloc((void**)&d_ab, (size_t)2 * nlanc * sizeof(double)));
       HIPCHK(hipMemsetAsync(d_ab, 0, (size_t)2 * nlanc * sizeof(double), h->stream));
-      const double s1 = 1.0 / bt, bprev = 1.0 / lz.s_cur;
-      const double init[2] = {s1, 1.0 / (s1 * bprev)};   // s_1 = 1/beta_1 ; c_1 = beta_1/beta_0, rounded like LzRunner::step()
-      const double one = 1.0;
-      hipError_t e1 = hipMemcpyAsync(h->d_scalars + 2, init, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
-      hipError_t e2 = hipMemcpyAsync(h->d_scalars + 6, &one, sizeof(double), hipMemcpyHostToDevice, h->stream);
-      if (e1 == hipSuccess && e2 == hipSuccess) e1 = hipStreamSynchronize(h->stream);
-      rc = (e1 != hipSuccess || e2 != hipSuccess) ? fail(HXV_ERR_HIP, "scalar upload failed") : lz.run_device_iterations(nlanc, d_ab, d_ab + nlanc, true);
+      rc = lz.begin_device_iterations(bt) != hipSuccess ? fail(HXV_ERR_HIP, "scalar upload failed") : lz.run_device_iterations(nlanc, d_ab, d_ab + nlanc, true);
       std::vector<double> ab((size_t)2 * nlanc, 0.0);
       if (rc == HXV_OK) {
         hipError_t e3 = hipMemcpyAsync(ab.data(), d_ab, ab.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
@@ -824,8 +826,7 @@ int hxv_lanczos_eigh(hxv_handle* h, int32_t nitermax, double threshold, double* 
   const bool real = want_real(h);  // the start vector is ours: real when H is (REAL-vector mode)
   int rc = comm_agree(h, ensure_lz(h, real));
   if (rc) return rc;
-  const int64_t nc = (int64_t)h->host.pitch * h->host.qdw;                      // this rank's slab
-  const int64_t n = real ? (int64_t)pitch_real_of(h) * h->host.qdw / 2 : nc;  // double2 elements per vector
+  const int64_t n = lz_len(h, real);
   const int g = grid_for(n);
   const int nmax = (int)std::min<int64_t>(nitermax, h->host.dim);
   const uint64_t seed = 0x5EED5EEDull;
@@ -834,13 +835,10 @@ int hxv_lanczos_eigh(hxv_handle* h, int32_t nitermax, double threshold, double* 
     if (real)
       launch_init_real(h, (double*)lz.b.w, seed, h->stream);
     else
-      hipLaunchKernelGGL(lz_init, dim3(g), dim3(256), 0, h->stream, n, lz.b.w, seed, h->host.dimup, h->host.pitch, h->host.dw0, h->dev.up_iperm, h->dev.up_sign);
+      launch_init(h, lz.b.w, seed, h->stream);
     HIPCHK(hipMemsetAsync(h->d_scalars, 0, 8 * sizeof(double), h->stream));
-    hipLaunchKernelGGL(lz_nrm, dim3(g), dim3(256), 0, h->stream, n, lz.b.w, h->d_partials + RED_BLOCKS);
-    int rcn = reduce_scalar(h, h->d_partials + RED_BLOCKS, g, 1, 1);
-    if (rcn) return rcn;
-    hipLaunchKernelGGL(lz_scale, dim3(g), dim3(256), 0, h->stream, n, lz.b.q, lz.b.w, h->d_scalars, 1);
-    return lz.begin(1.0);
+    int rcn = enqueue_normalise(h, lz.b.q, lz.b.w, n, LZ_BETA);
+    return rcn ? rcn : lz.begin(1.0);
   };
   LzRunner lz(h, h->lz_vec[0], h->lz_vec[1], h->lz_vec[2], real);
   rc = start(lz);
@@ -908,10 +906,8 @@ int hxv_lanczos_eigh(hxv_handle* h, int32_t nitermax, double threshold, double* 
       if (rc) return rc;
     }
     // normalise the Ritz vector
-    hipLaunchKernelGGL(lz_nrm, dim3(g), dim3(256), 0, h->stream, n, out, h->d_partials + RED_BLOCKS);
-    rc = reduce_scalar(h, h->d_partials + RED_BLOCKS, g, 1, 1);
+    rc = enqueue_normalise(h, out, out, n, LZ_BETA);
     if (rc) return rc;
-    hipLaunchKernelGGL(lz_scale, dim3(g), dim3(256), 0, h->stream, n, out, out, h->d_scalars, 1);
     if (real) {
       // the Ritz vector was accumulated as a real vector in d_vect's memory: expand it to the complex layout of the API
       HIPCHK(hipMemcpyAsync(h->lz_vec[2], out, (size_t)n * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
@@ -932,16 +928,14 @@ int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_v
   if (!h || !d_vin_a || !d_vin_b || nlanc < 1 || !alanc_a || !blanc_a || !alanc_b || !blanc_b)
     return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair: bad argument");
   if (const char* why = real_mode_blocker(h)) return fail(HXV_ERR_UNSUPPORTED, std::string("hxv_lanczos_tridiag_pair: unavailable: ") + why);
-  if (h->host.nranks != 1 && !comm_ready(h))
-    return fail(HXV_ERR_STATE, "device Lanczos on a split sector needs the communicator: call hxv_comm_init after opening the sector");
+  if (int rcc = need_comm(h, "device Lanczos")) return rcc;
   if (!h->lz_fused) return fail(HXV_ERR_UNSUPPORTED, "hxv_lanczos_tridiag_pair needs the fused recurrence (option lanczos_fused)");
   HIPCHK(hipSetDevice(h->device));
   StageFree staged{h, {nullptr, nullptr}};
-  const bool dist = comm_ready(h);
-  const int64_t n = (int64_t)h->host.pitch * h->host.qdw;
+  const int64_t n = lz_len(h, false);
   const int g = grid_for(n);
-  const int64_t nwg = std::max<int64_t>(1, tiled_pass_up_workgroups(h->dev, h->plan, false, dw_part_in_pieces(h)));
-  // scalars: [0] alpha_a [1] beta_a [2] s_a [3] c_a [4] alpha_a*s_a ; [8..12] the same for b ; block partials behind them
+  // scalars: the LzSlot block of component a, the one of b LZ_PAIR behind it (the handle's d_scalars has room for one only); the block
+  // partials of the start vectors' check behind them
   double* d_sc = nullptr;
   // every rank-local preparation that can fail comes BEFORE the agreement: a rank that cannot go on makes all ranks return
   auto prepare = [&]() -> int {
@@ -949,16 +943,9 @@ int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_v
     if (!r) r = stage_start_vector(h, d_vin_b, &staged.p[1]);
     if (!r) r = ensure_lz(h, false);  // (split sector: vectors are this rank's slab, every sum below is all-reduced)
     if (!r) r = ensure_wt(h);
+    if (!r) r = ensure_lz_partial(h, 2 * lz_pass_a_workgroups(h, false));
     if (r) return r;
-    if (2 * nwg > h->lz_partial_n) {
-      if (h->d_lz_partial) (void)hipFree(h->d_lz_partial);
-      h->d_lz_partial = nullptr;
-      h->lz_partial_n = 0;
-      HIPCHK(hipMalloc((void**)&h->d_lz_partial, (size_t)2 * nwg * sizeof(double)));
-      HIPCHK(hipMemsetAsync(h->d_lz_partial, 0, (size_t)2 * nwg * sizeof(double), h->stream));  // (a rank without columns launches nothing)
-      h->lz_partial_n = 2 * nwg;
-    }
-    HIPCHK(hipMalloc((void**)&d_sc, (size_t)(16 + 3 * RED_BLOCKS) * sizeof(double)));
+    HIPCHK(hipMalloc((void**)&d_sc, (size_t)(2 * LZ_PAIR + 3 * RED_BLOCKS) * sizeof(double)));
     return HXV_OK;
   };
   int rc = comm_agree(h, prepare());
@@ -969,77 +956,43 @@ int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_v
     }
   } guard{d_sc};
   if (rc) return rc;
-  double* d_p0 = d_sc + 16;
+  double* d_p0 = d_sc + 2 * LZ_PAIR;
   double* d_p1 = d_p0 + RED_BLOCKS;
   double* d_p2 = d_p1 + RED_BLOCKS;
-  HIPCHK(hipMemsetAsync(d_sc, 0, 16 * sizeof(double), h->stream));
-  // d_sc[slot] = sum (op 0) or 2-norm (op 1) of `np` partial sums -- over all ranks on a split sector
-  auto reduce = [&](const double* part, int np, int slot, int op) -> int {
-    hipLaunchKernelGGL(lz_final, dim3(1), dim3(256), 0, h->stream, part, np, d_sc, slot, dist ? 0 : op);
-    if (dist) {
-      if (int rca = comm_allreduce_sum(h, d_sc + slot, 1, h->stream)) return rca;
-      if (op) hipLaunchKernelGGL(lz_sqrt, dim3(1), dim3(1), 0, h->stream, d_sc, slot);
-    }
-    return HXV_OK;
-  };
+  HIPCHK(hipMemsetAsync(d_sc, 0, 2 * LZ_PAIR * sizeof(double), h->stream));
   double2 *q = h->lz_vec[0], *qm = h->lz_vec[1], *w = h->lz_vec[2];
   hipLaunchKernelGGL(lz_pack_pair, dim3(g), dim3(256), 0, h->stream, n, (const double2*)d_vin_a, (const double2*)d_vin_b, q, d_p0, d_p1, d_p2);
-  if ((rc = reduce(d_p0, g, 5, 0)) || (rc = reduce(d_p1, g, 6, 1)) || (rc = reduce(d_p2, g, 7, 1))) return rc;
+  // (its own block: the three sums of the check sit in a row from LZ_TMP on)
+  if ((rc = reduce_scalar(h, d_p0, g, LZ_TMP, 0, d_sc)) || (rc = reduce_scalar(h, d_p1, g, LZ_TMP + 1, 1, d_sc)) || (rc = reduce_scalar(h, d_p2, g, LZ_TMP + 2, 1, d_sc))) return rc;
   double head[3];
-  HIPCHK(hipMemcpyAsync(head, d_sc + 5, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(head, d_sc + LZ_TMP, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   if (head[0] != 0.0) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair: the start vectors must be real (zero imaginary parts)");
   for (int c = 0; c < 2; ++c)
     if (!(head[1 + c] > 0.0) || !std::isfinite(head[1 + c])) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair: a start vector is zero or not finite");
   for (int k = 0; k < nlanc; ++k) alanc_a[k] = blanc_a[k] = alanc_b[k] = blanc_b[k] = 0.0;
-  // per component, exactly LzRunner's fused recurrence: q = s*X, s = 1/beta_k (the start vector's norm carried as beta_0)
-  double s_cur[2], beta_prev[2];
+  // per component, LzRunner's fused recurrence: q = s*X, s = 1/beta_k (the start vector's norm carried as beta_0)
+  LzScale scale[2];
   bool alive[2] = {true, true};
   int done[2] = {0, 0};
-  for (int c = 0; c < 2; ++c) {
-    const double nrm = std::fabs(head[1 + c] - 1.0) <= 1e-14 ? 1.0 : head[1 + c];
-    s_cur[c] = 1.0 / nrm;
-    beta_prev[c] = nrm;
-  }
+  for (int c = 0; c < 2; ++c) scale[c].begin(std::fabs(head[1 + c] - 1.0) <= 1e-14 ? 1.0 : head[1 + c]);
   double* al[2] = {alanc_a, alanc_b};
   double* bl[2] = {blanc_a, blanc_b};
   bool first = true;
   for (int k = 0; k < nlanc && (alive[0] || alive[1]); ++k) {
-    double sc[16] = {0};
+    double up[2][2];  // -> LZ_S, LZ_C of each component (a finished one is multiplied away: the other one goes on alone)
     for (int c = 0; c < 2; ++c) {
-      sc[8 * c + 2] = alive[c] ? s_cur[c] : 0.0;  // (a finished component is multiplied away: the other one goes on alone)
-      sc[8 * c + 3] = (first || !alive[c]) ? 0.0 : 1.0 / (s_cur[c] * beta_prev[c]);
+      up[c][0] = alive[c] ? scale[c].s_cur : 0.0;
+      up[c][1] = (first || !alive[c]) ? 0.0 : scale[c].c();
+      HIPCHK(hipMemcpyAsync(d_sc + c * LZ_PAIR + LZ_S, up[c], 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    HIPCHK(hipMemcpyAsync(d_sc + 2, sc + 2, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_sc + 10, sc + 10, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    LzEpilogue ep;
-    ep.xm = first ? nullptr : qm;
-    ep.scal = d_sc;
-    ep.i_s = 2;
-    ep.i_c = 3;
-    ep.pair = 1;
-    ep.i_s2 = 10;
-    ep.i_c2 = 11;
-    ep.partial = h->d_lz_partial;
-    ep.partial2 = h->d_lz_partial + nwg;
-    if (dist) {  // exchange + product (every rank takes this branch together)
-      if ((rc = apply_slab(h, q, w, h->stream, &ep))) return rc;
-    } else {
-      hipError_t e = launch_hxv_tiled(h->dev, h->plan, q, h->d_wt, w, h->stream, &ep);
-      if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-      h->n_apply++;
-    }
-    if ((rc = reduce(h->d_lz_partial, (int)nwg, 0, 0)) || (rc = reduce(h->d_lz_partial + nwg, (int)nwg, 8, 0))) return rc;
-    hipLaunchKernelGGL(lz_mul, dim3(1), dim3(1), 0, h->stream, d_sc, 4, 0, 2);
-    hipLaunchKernelGGL(lz_mul, dim3(1), dim3(1), 0, h->stream, d_sc, 12, 8, 10);
-    hipLaunchKernelGGL(lz_sub_nrm_pair, dim3(g), dim3(256), 0, h->stream, n, w, q, d_sc, 4, 12, d_p0, d_p1);
-    if ((rc = reduce(d_p0, g, 1, 1)) || (rc = reduce(d_p1, g, 9, 1))) return rc;
-    double host[16];
-    HIPCHK(hipMemcpyAsync(host, d_sc, 16 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = fused_step_enqueue(h, false, q, first ? nullptr : qm, w, d_sc, true))) return rc;
+    double host[2 * LZ_PAIR];
+    HIPCHK(hipMemcpyAsync(host, d_sc, sizeof(host), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int c = 0; c < 2; ++c) {
       if (!alive[c]) continue;
-      const double a = host[8 * c], bt = host[8 * c + 1];
+      const double a = host[c * LZ_PAIR + LZ_ALPHA], bt = host[c * LZ_PAIR + LZ_BETA];
       al[c][k] = a;
       if (k + 1 < nlanc) bl[c][k + 1] = bt;
       done[c] = k + 1;
@@ -1047,8 +1000,7 @@ int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_v
         alive[c] = false;  // breakdown of this component's Krylov space (the early exit of hxv_lanczos_tridiag)
         continue;
       }
-      beta_prev[c] = 1.0 / s_cur[c];
-      s_cur[c] = 1.0 / bt;
+      scale[c].next(bt);
     }
     // rotate: X_{k+1} = w (unnormalised residual), X_k = q, the old X_{k-1} becomes the next output
     double2* old_m = qm;
@@ -1285,12 +1237,10 @@ int hxv_apply_ladder_axpy(hxv_handle* from, hxv_handle* to, int32_t orbital, int
     release();  // (synchronises the stream: the host lists above are read by asynchronous copies)
   }
   if (norm2) {
-    const int64_t n = (int64_t)b.pitch * b.qdw;  // pads of d_out must be zero (hxv.h)
-    const int g = grid_for(n);
-    hipLaunchKernelGGL(lz_nrm, dim3(g), dim3(256), 0, st, n, (const double2*)d_out, to->d_partials);
-    int rcn = reduce_scalar(to, to->d_partials, g, 5, 0);  // <out|out> over ALL ranks of a split sector
+    // <out|out> over ALL ranks of a split sector (pads of d_out must be zero: hxv.h)
+    int rcn = enqueue_norm(to, (const double2*)d_out, (int64_t)b.pitch * b.qdw, LZ_TMP, 0);
     if (rcn) return rcn;
-    HIPCHK(hipMemcpyAsync(norm2, to->d_scalars + 5, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(norm2, to->d_scalars + LZ_TMP, sizeof(double), hipMemcpyDeviceToHost, st));
   }
   HIPCHK(hipStreamSynchronize(st));
   return HXV_OK;
@@ -1304,20 +1254,16 @@ int hxv_time_lanczos(hxv_handle* h, void* d_work3, int32_t nrep, float* ms_per_i
   HIPCHK(hipMemsetAsync(d_work3, 0, (size_t)3 * n * sizeof(double2), h->stream));
   const bool real = want_real(h);
   LzRunner lz(h, (double2*)d_work3, (double2*)d_work3 + n, (double2*)d_work3 + 2 * n, real);
-  const int64_t nfull = n;
   n = lz.n2;
-  const int g = grid_for(n);
   if (real)
     launch_init_real(h, (double*)lz.b.w, 0x1234ull, h->stream);
   else
-    hipLaunchKernelGGL(lz_init, dim3(g), dim3(256), 0, h->stream, n, lz.b.w, 0x1234ull, h->host.dimup, h->host.pitch, 0, h->dev.up_iperm, h->dev.up_sign);
-  (void)nfull;
+    launch_init(h, lz.b.w, 0x1234ull, h->stream);
   HIPCHK(hipMemsetAsync(h->d_scalars, 0, 8 * sizeof(double), h->stream));
-  hipLaunchKernelGGL(lz_nrm, dim3(g), dim3(256), 0, h->stream, n, lz.b.w, h->d_partials + RED_BLOCKS);
-  hipLaunchKernelGGL(lz_final, dim3(1), dim3(256), 0, h->stream, h->d_partials + RED_BLOCKS, g, h->d_scalars, 1, 1);
-  hipLaunchKernelGGL(lz_scale, dim3(g), dim3(256), 0, h->stream, n, lz.b.q, lz.b.w, h->d_scalars, 1);
+  int rc = enqueue_normalise(h, lz.b.q, lz.b.w, n, LZ_BETA);
+  if (rc) return rc;
   HIPCHK(hipMemsetAsync(lz.b.qm, 0, (size_t)n * sizeof(double2), h->stream));
-  int rc = lz.begin(1.0);
+  rc = lz.begin(1.0);
   if (rc) return rc;
   double a, bt;
   rc = lz.step(&a, &bt);  // untimed first step (lazy allocations)
@@ -1326,12 +1272,7 @@ int hxv_time_lanczos(hxv_handle* h, void* d_work3, int32_t nrep, float* ms_per_i
     // the fixed-length device-only path of hxv_lanczos_tridiag: iterations 1..nrep, three per hipGraph
     double* d_ab = nullptr;
     HIPCHK(hipMalloc((void**)&d_ab, (size_t)2 * (nrep + 1) * sizeof(double)));
-    const double s1 = 1.0 / bt, bprev = 1.0 / lz.s_cur;
-    const double init[2] = {s1, 1.0 / (s1 * bprev)};
-    const double one = 1.0;
-    hipError_t e = hipMemcpyAsync(h->d_scalars + 2, init, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->d_scalars + 6, &one, sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    hipError_t e = lz.begin_device_iterations(bt);
     if (e == hipSuccess) e = hipEventRecord(h->ev0, h->stream);
     rc = e != hipSuccess ? fail(HXV_ERR_HIP, std::string("hxv_time_lanczos: ") + hipGetErrorString(e))
                          : lz.run_device_iterations(nrep + 1, d_ab, d_ab + nrep + 1, true);
