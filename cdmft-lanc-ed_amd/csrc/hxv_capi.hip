@@ -864,6 +864,9 @@ int64_t hxv_get_option(const hxv_handle* h, const char* name) {
   if (!strcmp(name, "eigh_last_local_passes")) return h->eigh_last_local;
   if (!strcmp(name, "eigh_last_search_products")) return h->eigh_last_search;  // *nmatvec of the last hxv_eigh_lowest = search + check
   if (!strcmp(name, "eigh_last_check_products")) return h->eigh_last_check;
+  if (!strcmp(name, "eigh_last_restarts")) return h->eigh_last_restarts;              // thick restarts of the search round
+  if (!strcmp(name, "eigh_last_fused_restarts")) return h->eigh_last_fused_restarts;  // ... whose rotation went through tr_rotate_dots
+  if (!strcmp(name, "eigh_last_fused_first_steps")) return h->eigh_last_fused_first;  // restart cycles begun by tr_axpy_mdot
   if (!strcmp(name, "lanczos_real_last")) return h->last_real;
   if (!strcmp(name, "slab_copies")) return h->n_slab_copy;  // exchanges whose vector was not at home in a gather buffer
   if (!strcmp(name, "lanczos_inplace")) return h->lz_inplace;
@@ -880,6 +883,23 @@ int64_t hxv_get_option(const hxv_handle* h, const char* name) {
   if (!strcmp(name, "p16_bits_dw")) return h->plan.dw.p16_bits;
   if (!strcmp(name, "lds_budget_kb_up")) return h->plan.opt.lds_budget_kb_up;
   if (!strcmp(name, "lds_budget_kb_dw")) return h->plan.opt.lds_budget_kb_dw;
+  // the remaining options a caller can set, as hxv_set_option stored them
+  if (!strcmp(name, "threads_up")) return h->plan.opt.threads_up;
+  if (!strcmp(name, "threads_dw")) return h->plan.opt.threads_dw;
+  if (!strcmp(name, "sort_mode")) return h->plan.opt.sort_mode;
+  if (!strcmp(name, "sort_mode_dw")) return h->plan.opt.sort_mode_dw;
+  if (!strcmp(name, "wt_cols")) return h->plan.opt.wt_cols;
+  if (!strcmp(name, "spread_banks")) return h->plan.opt.spread_banks;
+  if (!strcmp(name, "job_cols")) return h->plan.opt.job_cols;
+  if (!strcmp(name, "job_groups")) return h->plan.opt.job_groups;
+  if (!strcmp(name, "job_stages")) return h->plan.opt.job_stages;
+  if (!strcmp(name, "job_max_blocks")) return h->plan.opt.job_max_blocks;
+  if (!strcmp(name, "pair_rows")) return h->plan.opt.pair_rows;
+  if (!strcmp(name, "block_order")) return h->plan.opt.block_order;
+  if (!strcmp(name, "lds_min_kb_up")) return h->plan.opt.lds_min_kb_up;
+  if (!strcmp(name, "lds_min_kb_dw")) return h->plan.opt.lds_min_kb_dw;
+  if (!strcmp(name, "fold_nd")) return h->dev.nd.fold;
+  if (!strcmp(name, "lanczos_fused")) return h->lz_fused;
   if (!strcmp(name, "k_in_up")) return h->plan.up.k_in;
   if (!strcmp(name, "k_out_up")) return h->plan.up.k_out;
   if (!strcmp(name, "k_in_dw")) return h->plan.dw.k_in;

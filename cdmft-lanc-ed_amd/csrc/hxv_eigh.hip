@@ -596,6 +596,7 @@ int hxv_eigh_lowest(hxv_handle* h, int32_t neigen, int32_t ncv, int32_t maxresta
   std::vector<double> lockval;  // eigenvalues of the locked vectors V[0..nlock)
   int nmv = 0, nconv = 0, ne = neigen;
   int n_full = 0, n_local = 0;  // Gram-Schmidt passes against the whole basis / against the two local vectors only
+  int n_restart = 0, n_fused_rot = 0, n_fused_first = 0;  // restarts of the search round / of those, rotated by tr_rotate_dots / cycles begun by tr_axpy_mdot
   bool closed = false;  // the Krylov space closed (invariant subspace): every returned pair is exact
   bool above = false;   // a check round stopped early: the lowest Ritz value minus its residual bound is already above `stop_above`
   const bool local_fused = lanczos_local_step_available(h);
@@ -683,6 +684,7 @@ int hxv_eigh_lowest(hxv_handle* h, int32_t neigen, int32_t ncv, int32_t maxresta
               hipLaunchKernelGGL(tr_colsum, dim3(1), dim3(256), 0, st, d_part, g, 2 * FUSE_NJ, 2 * (jt + 1), d_coef, real ? 1 : 0);
               HIPCHK(hipStreamSynchronize(st));  // (cf is a host buffer)
               first_dots_ready = true;
+              ++n_fused_first;
             } else {
               for (int l = 0; l < k; ++l) {
                 isel[l] = nlock + l;
@@ -858,6 +860,8 @@ int hxv_eigh_lowest(hxv_handle* h, int32_t neigen, int32_t ncv, int32_t maxresta
         HIPCHK(hipMemcpyAsync(av(k), av(ma), (size_t)n * sizeof(double2), hipMemcpyDeviceToDevice, st));
       }
       HIPCHK(hipStreamSynchronize(st));  // Ssc (host) is reused at the next restart
+      if (nlock == 0) ++n_restart;
+      if (fuse_rot) ++n_fused_rot;
       for (int i = 0; i < k; ++i) nv[nlock + i] = 1.0;
       nv[nlock + k] = nv[nlock + ma];
       if (!h->eigh_measure_all) {
@@ -949,6 +953,9 @@ int hxv_eigh_lowest(hxv_handle* h, int32_t neigen, int32_t ncv, int32_t maxresta
   h->eigh_last_local = n_local;
   h->eigh_last_search = nmv_search;
   h->eigh_last_check = nmv - nmv_search;
+  h->eigh_last_restarts = n_restart;
+  h->eigh_last_fused_restarts = n_fused_rot;
+  h->eigh_last_fused_first = n_fused_first;
   if (d_evecs) {
     for (int i = 0; i < ne; ++i) {
       if (real)

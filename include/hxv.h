@@ -475,7 +475,8 @@ int hxv_get_diag(const hxv_handle *h, double *diag);
  *   Pass A as pipelined jobs (LDS-DMA tile ring, one workgroup per CU): "job_up" 2 [default: for the fused Lanczos product only] |
  *   1 (always) | 0 (one tile per workgroup), "job_groups" columns per job [about 100], "job_cols" 1, "job_stages" ring depth 2..8 [4],
  *   "job_max_blocks" [32].  The engine falls back to the one-tile kernels where jobs do not apply (real vectors, stored diagonal, more than
- *   24 in-block / 16 out-of-block entries per row, blocks over 960 rows).
+ *   24 in-block entries per row, more than 8 out-of-block partners -- row slots plus block hops -- of a block, blocks over 960 rows;
+ *   get "job_up_active" tells whether a plain product with "job_up" = 1 runs as jobs).
  *   "wt_colmajor" 0|1 [1: the blocked dw-hop scratch holds column-major patches -- pass A's accumulator init reads R*16 contiguous bytes per column
  *   and patch instead of every lane its own 64-byte stretch; bit-identical],
  *   "real_dw_pairs" 0|1 [1: pass B of the REAL-vector product runs the complex kernel on pairs of rows -- one table decode and one 16-byte LDS
@@ -489,7 +490,11 @@ int hxv_get_diag(const hxv_handle *h, double *diag);
  *
  * hxv_get_option additionally reports plan statistics ("tile_bits_up", "nblocks_up", "slots_in_up_x100", "max_outer_up", "job_up_active", ...),
  * driver read-backs ("lanczos_real_last", "eigh_last_full_passes", "eigh_last_local_passes", "eigh_last_search_products",
- * "eigh_last_check_products", "slab_copies") and what the open cost ("open_cache_hit", "open_us_host|plan|upload|total").        */
+ * "eigh_last_check_products", "slab_copies"; which restart code the last hxv_eigh_lowest ran: "eigh_last_restarts" thick restarts of the search
+ * round, "eigh_last_fused_restarts" those whose rotation also measured the residual vector, "eigh_last_fused_first_steps" restart cycles whose
+ * first step removed the arrow and measured in one pass) and what the open cost ("open_cache_hit", "open_us_host|plan|upload|total").
+ * Every option of groups 1 and 2 reads back the value hxv_set_option stored ("tile_bits_up|_dw": the block bits of the plan in use;
+ * "rows_per_tile" 0: the 4 or 8 it resolved to; "lds_budget_kb": through its "_up" / "_dw" halves); -1 is the answer to an unknown name. */
 int hxv_set_option(hxv_handle *h, const char *name, int64_t value);
 int64_t hxv_get_option(const hxv_handle *h, const char *name);
 
