@@ -23,6 +23,15 @@
 
 namespace hxv {
 
+// f(integral_constant<min(l, N)>) for l >= 1, nothing for l <= 0: code specialised on a small wave-uniform count
+template <int N, typename F>
+__device__ __forceinline__ void with_live_count(int l, F&& f) {
+  if (l >= N)
+    f(std::integral_constant<int, N>());
+  else if constexpr (N > 1)
+    with_live_count<N - 1>(l, f);
+}
+
 // ---------------------------------------------------------------------------------------
 // pass A
 // ---------------------------------------------------------------------------------------
@@ -437,29 +446,37 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, 
     else
       return ccol(it) * pitchb + rowb;
   };
+  // NP is sized for the largest block: in a smaller one the last pair iterations of a wave can lie past the block altogether (C3: a
+  // fifth of all wave iterations).  That is a wave-uniform fact -- the iterations [nlive, NP) of this wave have no live lane -- and
+  // nothing is issued for them: no tile load, no block hop's load, no row slot's word or gather, no add into the tile.  Waves that
+  // are partly live keep the clamped column.
+  const int wcol0 = __builtin_amdgcn_readfirstlane(tid) >> LR;  // the wave's first column of pair 0 (every lane is active here)
+  int nlive = 0;
+#pragma unroll
+  for (int it = 0; it < NP; ++it) nlive += (wcol0 + it * cstep < n || (t.debug & 4096)) ? 1 : 0;
+  const uint32_t rs0 = t.rs_ptr[kb], rs_end = (t.debug & 512) ? rs0 : t.rs_ptr[kb + 1];
   // phase 0: tile load
-  if (s.vcol_identity) {
-    const char* __restrict__ src = vrows + (int64_t)cb0 * pitchb;
+  {
     VT x[NP];
+    if (s.vcol_identity) {
+      const char* __restrict__ src = vrows + (int64_t)cb0 * pitchb;
 #pragma unroll
-    for (int it = 0; it < NP; ++it) x[it] = *reinterpret_cast<const VT*>(src + voff(it));
+      for (int it = 0; it < NP; ++it)
+        if (it < nlive) x[it] = *reinterpret_cast<const VT*>(src + voff(it));
+    } else {
+      uint32_t slot[NP];
 #pragma unroll
-    for (int it = 0; it < NP; ++it) {
-      if ((tid >> LR) + it * cstep < n) lds_st<VT>(tq + it * T * VB, x[it]);
+      for (int it = 0; it < NP; ++it)
+        if (it < nlive) slot[it] = s.vcol[cb0 + ccol(it)];
+#pragma unroll
+      for (int it = 0; it < NP; ++it)
+        if (it < nlive) x[it] = *reinterpret_cast<const VT*>(vrows + ((uint64_t)slot[it] * pitchb + rowb));
     }
-  } else {
-    uint32_t slot[NP];
-#pragma unroll
-    for (int it = 0; it < NP; ++it) slot[it] = s.vcol[cb0 + ccol(it)];
-    VT x[NP];
-#pragma unroll
-    for (int it = 0; it < NP; ++it) x[it] = *reinterpret_cast<const VT*>(vrows + ((uint64_t)slot[it] * pitchb + rowb));
 #pragma unroll
     for (int it = 0; it < NP; ++it) {
-      if ((tid >> LR) + it * cstep < n) lds_st<VT>(tq + it * T * VB, x[it]);
+      if (it < nlive && (tid >> LR) + it * cstep < n) lds_st<VT>(tq + it * T * VB, x[it]);
     }
   }
-  const uint32_t rs0 = t.rs_ptr[kb], rs_end = (t.debug & 512) ? rs0 : t.rs_ptr[kb + 1];
   __syncthreads();
   // in-block hops, one column per thread (plan guarantees n <= blockDim.x)
   {
@@ -516,20 +533,22 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, 
   if (!(t.debug & 1)) {
     constexpr int HB = NP > 4 ? 4 : NP;
     const char* __restrict__ vrow64 = vrows + rowb;  // per-thread 64-bit base of the row-slot gathers
+    // One group of HB pairs, compiled once per number L of its pairs that have a live lane in this wave (the live ones come first):
+    // straight-line code for every L, so the register arrays stay arrays of registers; L = HB is the kernel as it was.
+    auto group = [&](auto lc, const int base) {
+      constexpr int L = decltype(lc)::value;
+      VT osum[L];
 #pragma unroll
-    for (int base = 0; base < NP; base += HB) {
-      VT osum[HB];
-#pragma unroll
-      for (int it = 0; it < HB; ++it) osum[it] = vzero<VT>();
+      for (int it = 0; it < L; ++it) osum[it] = vzero<VT>();
       // block hops: source column slot = start + column offset, one signed coefficient for the whole block
       for (uint32_t h = t.bh_ptr[kb]; h < ((t.debug & 256) ? t.bh_ptr[kb] : t.bh_ptr[kb + 1]); ++h) {
         const CT cf = lds_ld<CT>(t.bh[2 * h + 1] << LCB);
         const char* __restrict__ src = vrows + (int64_t)t.bh[2 * h] * pitchb;
-        VT x[HB];
+        VT x[L];
 #pragma unroll
-        for (int it = 0; it < HB; ++it) x[it] = *reinterpret_cast<const VT*>(src + voff(base + it));
+        for (int it = 0; it < L; ++it) x[it] = *reinterpret_cast<const VT*>(src + voff(base + it));
 #pragma unroll
-        for (int it = 0; it < HB; ++it) Coef<REAL>::fma(osum[it], cf, x[it]);
+        for (int it = 0; it < L; ++it) Coef<REAL>::fma(osum[it], cf, x[it]);
       }
       // row slots: one table word per column of the block and (block, source block) pair; the words of SB slots
       // are fetched together so that the gathers that depend on them follow one table round trip, not SB
@@ -537,13 +556,13 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, 
       //  keep eight-pair tiles from spilling, for no measurable gain)
       constexpr int SB = 2;
       for (uint32_t sl0 = rs0; sl0 < rs_end; sl0 += SB) {
-        uint32_t e[SB][HB];
+        uint32_t e[SB][L];
 #pragma unroll
         for (int jj = 0; jj < SB; ++jj) {
           if (sl0 + jj < rs_end) {  // uniform
             const uint32_t* __restrict__ tab = t.rs_tab + t.rs_off[sl0 + jj];
 #pragma unroll
-            for (int it = 0; it < HB; ++it) e[jj][it] = tab[ccol(base + it)];
+            for (int it = 0; it < L; ++it) e[jj][it] = tab[ccol(base + it)];
           }
         }
 #pragma unroll
@@ -551,16 +570,16 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, 
           if (sl0 + jj < rs_end) {
             bool none = true;
 #pragma unroll
-            for (int it = 0; it < HB; ++it) none = none && (e[jj][it] == emptyz);
+            for (int it = 0; it < L; ++it) none = none && (e[jj][it] == emptyz);
             if (__all(none)) continue;
-            VT x[HB];
+            VT x[L];
             const char* __restrict__ vslot = vrow64 + (uint64_t)t.rs_base[sl0 + jj] * pitchb;  // (the slot's source block)
             const bool neg = t.rs_neg[sl0 + jj] != 0;  // (uniform: the shared table holds the other overall sign)
 #pragma unroll
-            for (int it = 0; it < HB; ++it)
+            for (int it = 0; it < L; ++it)
               x[it] = *reinterpret_cast<const VT*>(vslot + (uint64_t)(e[jj][it] & TILE_OFF_MASK) * pitchb);
 #pragma unroll
-            for (int it = 0; it < HB; ++it) {
+            for (int it = 0; it < L; ++it) {
               CT cf = lds_ld<CT>((e[jj][it] >> TILE_COEF_SHIFT) << LCB);
               if (neg) cf = Coef<REAL>::neg(cf);
               Coef<REAL>::fma(osum[it], cf, x[it]);
@@ -569,7 +588,7 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, 
         }
       }
 #pragma unroll
-      for (int it = 0; it < HB; ++it) {
+      for (int it = 0; it < L; ++it) {
         if ((tid >> LR) + (base + it) * cstep < n) {
           const uint32_t q = tq + (base + it) * T * VB;
           VT a = lds_ld<VT>(q);
@@ -577,7 +596,9 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, 
           lds_st<VT>(q, a);
         }
       }
-    }
+    };
+#pragma unroll
+    for (int base = 0; base < NP; base += HB) with_live_count<HB>(nlive - base, [&](auto lc) { group(lc, base); });  // (uniform)
   }
   __syncthreads();
   const int cl0 = max(cb0, s.dw0) - s.dw0, cl1 = min(cb0 + n, s.dw0 + s.qdw) - s.dw0;  // local output columns [cl0,cl1)

@@ -58,6 +58,9 @@ struct SpinTiles {
   uint32_t* d_order_pc = nullptr;    // [nblocks] block indices by the particle number of the high orbitals (TileOptions::block_order)
 };
 
+// bits of TileOptions::debug that leave the results bit-identical (DevTiles::debug): the others are timing experiments with wrong results
+constexpr int TILE_DEBUG_EXACT = 4096;
+
 struct TileOptions {
   int cols_per_tile = 4;      // pass A (up hops): columns per workgroup tile
   int rows_per_tile = 0;      // pass B (dw hops): rows per workgroup tile; 0 = by sector size (4; 8 = whole 128-byte lines when the
@@ -85,7 +88,7 @@ struct TileOptions {
   int job_groups = 100; // column groups per job (about: an XCD's groups are cut into equal runs)
   int job_stages = 4;  // depth of the LDS tile ring (clamped to what fits 160 KB)
   int job_debug = 0;   // timing experiments only (JobUp::debug); results are wrong when non-zero
-  int debug = 0;   // timing experiments only (see DevTiles::debug); results are wrong when non-zero
+  int debug = 0;   // timing experiments only (see DevTiles::debug); results are wrong when a bit other than 4096 is set
   int passes = 3;     // bit 0: pass A (diag + up hops), bit 1: pass B (dw hops); timing experiments only
 };
 

@@ -487,6 +487,8 @@ int hxv_get_diag(const hxv_handle *h, double *diag);
  *
  * 3. TIMING EXPERIMENTS (results are wrong or partial when set; refused unless HXV_EXPERIMENTS=1 is in the environment)
  *   "passes" 1|2|3 [3], "debug" bit mask, "job_debug" bit mask.
+ *   One bit of the debug mask leaves the results bit-identical (same gate): 4096, pass B issues its loads also for the pair iterations no
+ *   lane of a wave owns (the kernel without the dead-wave skip, for A/B timings).
  *
  * hxv_get_option additionally reports plan statistics ("tile_bits_up", "nblocks_up", "slots_in_up_x100", "max_outer_up", "job_up_active", ...),
  * driver read-backs ("lanczos_real_last", "eigh_last_full_passes", "eigh_last_local_passes", "eigh_last_search_products",
