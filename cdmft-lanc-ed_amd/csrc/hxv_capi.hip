@@ -868,6 +868,7 @@ int64_t hxv_get_option(const hxv_handle* h, const char* name) {
   if (!strcmp(name, "eigh_last_fused_restarts")) return h->eigh_last_fused_restarts;  // ... whose rotation went through tr_rotate_dots
   if (!strcmp(name, "eigh_last_fused_first_steps")) return h->eigh_last_fused_first;  // restart cycles begun by tr_axpy_mdot
   if (!strcmp(name, "lanczos_real_last")) return h->last_real;
+  if (!strcmp(name, "pass_b_order_last")) return h->plan.dw_order_last;  // phase order the last pass-B launch ran (0 / 1; -1: none yet)
   if (!strcmp(name, "slab_copies")) return h->n_slab_copy;  // exchanges whose vector was not at home in a gather buffer
   if (!strcmp(name, "lanczos_inplace")) return h->lz_inplace;
   if (!strcmp(name, "exchange_overlap")) return h->a2a_overlap;

@@ -33,8 +33,9 @@ struct DevTiles {
   int nblocks, nscoef;
   int debug;  // timing experiments only: 1 skip out-of-block hops, 2 skip in-block hops, 8 plain instead of streaming hv stores (pass A),
               // 32 natural block order, 64 no packed row-slot words, 256 skip the block hops only, 512 skip the row slots only (round 6's
-              // phase budget: profiles/r06_phase_ablate_c3.log).  One bit leaves the results bit-identical: 4096 pass B issues its loads
-              // also for the pair iterations no lane of a wave owns (the kernel as it was before the dead-wave skip)
+              // phase budget: profiles/r06_phase_ablate_c3.log).  Two bits leave the results bit-identical: 4096 pass B issues its loads
+              // also for the pair iterations no lane of a wave owns (the kernel as it was before the dead-wave skip); 8192 pass B runs its
+              // phases in the earlier order, out-of-block sums added into the tile (hxv_pass_dw's ORD 0; read by the launcher)
   int pair_rows;  // pass B: the two row groups that share 128-byte lines run back to back, block by block (large sectors)
   const uint32_t* order;  // [nblocks] blocks by decreasing size (= grouped by table class), or null: pass B visits a row group's blocks in this order
   int p16_bits;           // ell16 words: (coefficient index << p16_bits) | offset, two per 32-bit word

@@ -372,13 +372,24 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_up(DevSector s, DevTiles t, 
 // pass B.  Tile element (column c of the block, row r) sits at pair index q = c*R + r in LDS, which is also the order the
 // lanes touch global memory in (lanes along the R contiguous rows of a column: coalesced 16*R-byte segments), so the
 // streaming phases address LDS linearly.  In the in-block phase a thread owns one column and its R rows: one table decode
-// serves R gathers at immediate offsets.  The out-of-block hops run afterwards, lanes along the rows again, after the
-// in-block sums have been parked in the tile.
+// serves R gathers at immediate offsets.  The out-of-block hops run lanes along the rows again: before the in-block phase with
+// their sums in registers, or after the in-block sums have been parked in the tile (ORD below).
 // The address arithmetic is kept off the vector ALU (it was more than half of this kernel's instructions): blockDim.x is a
 // multiple of R, so a thread's pairs all have the same row; every global access is a uniform 64-bit base plus a per-thread
 // 32-bit byte offset that is computed once (tile load, block hops, scratch store), or one 64-bit multiply-add (row slots).
 // ---------------------------------------------------------------------------------------
-template <int R, int NP, bool REAL, bool P16, typename VT>
+// ORD, the order of the phases (chosen by the launcher, launch_dw_np):
+//   0  tile load | in-block hops | park the sums in the tile | out-of-block hops, each sum added into the tile | store from the tile
+//   1  tile load | out-of-block hops with their sums kept in registers, in-block hops (no barrier in between: a wave that has its
+//      gathers starts its LDS work while others still gather) | park | own elements of the tile + register sums, stored straight from
+//      the registers: one barrier and one read-modify-write pass over the tile fewer, and the out-of-block gathers (global memory only,
+//      they depend on nothing in the tile) no longer wait behind the LDS-only phase.  A thread's pairs are then the ones of the blocked
+//      store: columns counted from the block's aligned scratch group, `sh` = 0 .. wc-1 columns in front of the block, so the first sh
+//      column positions of a workgroup are dead lanes (plan: max_block + wc - 1 columns fit NP sweeps).
+//      (With the gathers ahead of the first barrier instead -- every wave then writes its own copy of the coefficient table -- C3 gained
+//      a third of what this placement gains: profiles/pass_b_phase_order_ab.log.)
+// The floating-point operations and their order are the same in every order.
+template <int R, int NP, bool REAL, bool P16, typename VT, int ORD = 0>
 __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, const VT* __restrict__ v, VT* __restrict__ wt,
                                                       int ngroups, int groups_per_xcd, int wc) {
   // NP = (row,column) pairs of the tile per thread (plan: max_block*R <= NP*blockDim.x); all their global
@@ -421,7 +432,14 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, 
   constexpr int LSW = 8 - LTB;                      // log2(columns per 256 B); LTB <= 7
   constexpr int LVB = VB == 8 ? 3 : 4;
   auto swz_of = [](uint32_t col) -> uint32_t { return ((col >> LSW) & (R - 1)) << LVB; };  // byte XOR of a column
-  const uint32_t tq = ltile + (((uint32_t)tid << LVB) ^ swz_of((uint32_t)tid >> LR));  // this thread's pair 0 (pair it: + it*T*VB)
+  constexpr bool REGS = ORD != 0;
+  static_assert(!REGS || NP <= 4, "the register sums of eight pairs do not fit");
+  // REGS: columns in front of the block in the thread-to-pair mapping (blocked scratch: the block start's misalignment to the group width)
+  const int sh = (REGS && wc) ? ((cb0 - s.dw0) & ((wc & 0xFF) - 1)) : 0;
+  const int c0 = (tid >> LR) - sh;  // column of this thread's pair 0 within the block (REGS: negative in a dead lane)
+  // this thread's pair 0 in the tile (pair it: + it*T*VB; a sweep advances the column by T/R, which leaves its swizzle bits alone)
+  const uint32_t tq = REGS ? ltile + (uint32_t)((c0 << LTB) + ((int)((uint32_t)(tid & (R - 1)) << LVB) ^ (int)swz_of((uint32_t)c0)))
+                           : ltile + (((uint32_t)tid << LVB) ^ swz_of((uint32_t)tid >> LR));
   const uint32_t emptyz = (uint32_t)(t.nscoef - 1) << TILE_COEF_SHIFT;
   const uint32_t p16m = (1u << t.p16_bits) - 1u;  // half-size table words: (coefficient index << p16_bits) | column
   for (int q = tid; q < t.nscoef; q += T) lds_st<CT>(q << LCB, Coef<REAL>::from(t.scoef[q]));
@@ -433,7 +451,8 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, 
   const char* __restrict__ vrows = reinterpret_cast<const char*>(v) + (int64_t)i0 * VB;  // uniform
   // column of pair `it` within the block (clamped) and its byte offset relative to (first column of a block, row i0);
   // the offsets are kept in registers when a thread has few pairs and recomputed (two instructions) when it has eight
-  auto ccol = [&](int it) -> uint32_t { return (uint32_t)min((tid >> LR) + it * cstep, n - 1); };
+  auto ccol = [&](int it) -> uint32_t { return (uint32_t)min(REGS && it == 0 ? max(c0, 0) : c0 + it * cstep, n - 1); };
+  auto owns = [&](int it) -> bool { return REGS ? (uint32_t)(c0 + it * cstep) < (uint32_t)n : c0 + it * cstep < n; };  // pair `it` lies in the block
   constexpr bool KEEP = NP <= 4 && R < 8;  // (eight-row tiles need the registers for their accumulators)
   uint32_t voff_keep[KEEP ? NP : 1];
   if constexpr (KEEP) {
@@ -450,7 +469,7 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, 
   // fifth of all wave iterations).  That is a wave-uniform fact -- the iterations [nlive, NP) of this wave have no live lane -- and
   // nothing is issued for them: no tile load, no block hop's load, no row slot's word or gather, no add into the tile.  Waves that
   // are partly live keep the clamped column.
-  const int wcol0 = __builtin_amdgcn_readfirstlane(tid) >> LR;  // the wave's first column of pair 0 (every lane is active here)
+  const int wcol0 = (__builtin_amdgcn_readfirstlane(tid) >> LR) - sh;  // the wave's first column of pair 0 (every lane is active here)
   int nlive = 0;
 #pragma unroll
   for (int it = 0; it < NP; ++it) nlive += (wcol0 + it * cstep < n || (t.debug & 4096)) ? 1 : 0;
@@ -474,10 +493,98 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, 
     }
 #pragma unroll
     for (int it = 0; it < NP; ++it) {
-      if (it < nlive && (tid >> LR) + it * cstep < n) lds_st<VT>(tq + it * T * VB, x[it]);
+      if (it < nlive && owns(it)) lds_st<VT>(tq + it * T * VB, x[it]);
     }
   }
+  // out-of-block hops: lanes along the contiguous rows again (coalesced R*16-byte segments of other columns, L2 of
+  // this XCD); ORD 0: the sums are added into the tile, each element by the one thread that owns the (row,column) pair;
+  // REGS: they stay in okeep until the store.
+  // Pairs are handled HB at a time to bound the registers (two 1024-thread workgroups per CU need <= 64 VGPRs).
+  VT okeep[REGS ? NP : 1];
+  if constexpr (REGS) {
+#pragma unroll
+    for (int it = 0; it < NP; ++it) okeep[it] = vzero<VT>();
+  }
+  auto out_of_block = [&]() {
+    if (t.debug & 1) return;
+    constexpr int HB = NP > 4 ? 4 : NP;
+    const char* __restrict__ vrow64 = vrows + rowb;  // per-thread 64-bit base of the row-slot gathers
+    // One group of HB pairs, compiled once per number L of its pairs that have a live lane in this wave (the live ones come first):
+    // straight-line code for every L, so the register arrays stay arrays of registers; L = HB is the kernel as it was.
+    auto group = [&](auto lc, const int base) {
+      constexpr int L = decltype(lc)::value;
+      // (REGS: one group, base = 0, and the sums are accumulated where they stay -- copying them out of the L-specialised code
+      //  afterwards let the compiler merge the copies of different L into one indexed store, which put half of okeep into scratch memory)
+      VT osum_own[REGS ? 1 : L];
+      VT* const osum = REGS ? okeep : osum_own;
+      if constexpr (!REGS) {
+#pragma unroll
+        for (int it = 0; it < L; ++it) osum[it] = vzero<VT>();
+      }
+      // block hops: source column slot = start + column offset, one signed coefficient for the whole block
+      for (uint32_t h = t.bh_ptr[kb]; h < ((t.debug & 256) ? t.bh_ptr[kb] : t.bh_ptr[kb + 1]); ++h) {
+        const CT cf = lds_ld<CT>(t.bh[2 * h + 1] << LCB);
+        const char* __restrict__ src = vrows + (int64_t)t.bh[2 * h] * pitchb;
+        VT x[L];
+#pragma unroll
+        for (int it = 0; it < L; ++it) x[it] = *reinterpret_cast<const VT*>(src + voff(base + it));
+#pragma unroll
+        for (int it = 0; it < L; ++it) Coef<REAL>::fma(osum[it], cf, x[it]);
+      }
+      // row slots: one table word per column of the block and (block, source block) pair; the words of SB slots
+      // are fetched together so that the gathers that depend on them follow one table round trip, not SB
+      // (the half-size, two-slots-per-word copy of these tables serves pass A only: here its decode costs the registers that
+      //  keep eight-pair tiles from spilling, for no measurable gain)
+      constexpr int SB = 2;
+      for (uint32_t sl0 = rs0; sl0 < rs_end; sl0 += SB) {
+        uint32_t e[SB][L];
+#pragma unroll
+        for (int jj = 0; jj < SB; ++jj) {
+          if (sl0 + jj < rs_end) {  // uniform
+            const uint32_t* __restrict__ tab = t.rs_tab + t.rs_off[sl0 + jj];
+#pragma unroll
+            for (int it = 0; it < L; ++it) e[jj][it] = tab[ccol(base + it)];
+          }
+        }
+#pragma unroll
+        for (int jj = 0; jj < SB; ++jj) {
+          if (sl0 + jj < rs_end) {
+            bool none = true;
+#pragma unroll
+            for (int it = 0; it < L; ++it) none = none && (e[jj][it] == emptyz);
+            if (__all(none)) continue;
+            VT x[L];
+            const char* __restrict__ vslot = vrow64 + (uint64_t)t.rs_base[sl0 + jj] * pitchb;  // (the slot's source block)
+            const bool neg = t.rs_neg[sl0 + jj] != 0;  // (uniform: the shared table holds the other overall sign)
+#pragma unroll
+            for (int it = 0; it < L; ++it)
+              x[it] = *reinterpret_cast<const VT*>(vslot + (uint64_t)(e[jj][it] & TILE_OFF_MASK) * pitchb);
+#pragma unroll
+            for (int it = 0; it < L; ++it) {
+              CT cf = lds_ld<CT>((e[jj][it] >> TILE_COEF_SHIFT) << LCB);
+              if (neg) cf = Coef<REAL>::neg(cf);
+              Coef<REAL>::fma(osum[it], cf, x[it]);
+            }
+          }
+        }
+      }
+      if constexpr (!REGS) {
+#pragma unroll
+        for (int it = 0; it < L; ++it) {
+          if ((tid >> LR) + (base + it) * cstep < n) {
+            const uint32_t q = tq + (base + it) * T * VB;
+            VT a = lds_ld<VT>(q);
+            vadd(a, osum[it]);
+            lds_st<VT>(q, a);
+          }
+        }
+      }
+    };
+#pragma unroll
+    for (int base = 0; base < NP; base += HB) with_live_count<HB>(nlive - base, [&](auto lc) { group(lc, base); });  // (uniform)
+  };
   __syncthreads();
+  if constexpr (REGS) out_of_block();
   // in-block hops, one column per thread (plan guarantees n <= blockDim.x)
   {
     VT acc[R];
@@ -527,81 +634,53 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_dw(DevSector s, DevTiles t, 
     }
   }
   __syncthreads();
-  // out-of-block hops: lanes along the contiguous rows again (coalesced R*16-byte segments of other columns, L2 of
-  // this XCD); the sums are added into the tile, each element by the one thread that owns the (row,column) pair.
-  // Pairs are handled HB at a time to bound the registers (two 1024-thread workgroups per CU need <= 64 VGPRs).
-  if (!(t.debug & 1)) {
-    constexpr int HB = NP > 4 ? 4 : NP;
-    const char* __restrict__ vrow64 = vrows + rowb;  // per-thread 64-bit base of the row-slot gathers
-    // One group of HB pairs, compiled once per number L of its pairs that have a live lane in this wave (the live ones come first):
-    // straight-line code for every L, so the register arrays stay arrays of registers; L = HB is the kernel as it was.
-    auto group = [&](auto lc, const int base) {
-      constexpr int L = decltype(lc)::value;
-      VT osum[L];
-#pragma unroll
-      for (int it = 0; it < L; ++it) osum[it] = vzero<VT>();
-      // block hops: source column slot = start + column offset, one signed coefficient for the whole block
-      for (uint32_t h = t.bh_ptr[kb]; h < ((t.debug & 256) ? t.bh_ptr[kb] : t.bh_ptr[kb + 1]); ++h) {
-        const CT cf = lds_ld<CT>(t.bh[2 * h + 1] << LCB);
-        const char* __restrict__ src = vrows + (int64_t)t.bh[2 * h] * pitchb;
-        VT x[L];
-#pragma unroll
-        for (int it = 0; it < L; ++it) x[it] = *reinterpret_cast<const VT*>(src + voff(base + it));
-#pragma unroll
-        for (int it = 0; it < L; ++it) Coef<REAL>::fma(osum[it], cf, x[it]);
-      }
-      // row slots: one table word per column of the block and (block, source block) pair; the words of SB slots
-      // are fetched together so that the gathers that depend on them follow one table round trip, not SB
-      // (the half-size, two-slots-per-word copy of these tables serves pass A only: here its decode costs the registers that
-      //  keep eight-pair tiles from spilling, for no measurable gain)
-      constexpr int SB = 2;
-      for (uint32_t sl0 = rs0; sl0 < rs_end; sl0 += SB) {
-        uint32_t e[SB][L];
-#pragma unroll
-        for (int jj = 0; jj < SB; ++jj) {
-          if (sl0 + jj < rs_end) {  // uniform
-            const uint32_t* __restrict__ tab = t.rs_tab + t.rs_off[sl0 + jj];
-#pragma unroll
-            for (int it = 0; it < L; ++it) e[jj][it] = tab[ccol(base + it)];
-          }
-        }
-#pragma unroll
-        for (int jj = 0; jj < SB; ++jj) {
-          if (sl0 + jj < rs_end) {
-            bool none = true;
-#pragma unroll
-            for (int it = 0; it < L; ++it) none = none && (e[jj][it] == emptyz);
-            if (__all(none)) continue;
-            VT x[L];
-            const char* __restrict__ vslot = vrow64 + (uint64_t)t.rs_base[sl0 + jj] * pitchb;  // (the slot's source block)
-            const bool neg = t.rs_neg[sl0 + jj] != 0;  // (uniform: the shared table holds the other overall sign)
-#pragma unroll
-            for (int it = 0; it < L; ++it)
-              x[it] = *reinterpret_cast<const VT*>(vslot + (uint64_t)(e[jj][it] & TILE_OFF_MASK) * pitchb);
-#pragma unroll
-            for (int it = 0; it < L; ++it) {
-              CT cf = lds_ld<CT>((e[jj][it] >> TILE_COEF_SHIFT) << LCB);
-              if (neg) cf = Coef<REAL>::neg(cf);
-              Coef<REAL>::fma(osum[it], cf, x[it]);
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int it = 0; it < L; ++it) {
-        if ((tid >> LR) + (base + it) * cstep < n) {
-          const uint32_t q = tq + (base + it) * T * VB;
-          VT a = lds_ld<VT>(q);
-          vadd(a, osum[it]);
-          lds_st<VT>(q, a);
-        }
-      }
-    };
-#pragma unroll
-    for (int base = 0; base < NP; base += HB) with_live_count<HB>(nlive - base, [&](auto lc) { group(lc, base); });  // (uniform)
+  if constexpr (!REGS) {
+    out_of_block();
+    __syncthreads();
   }
-  __syncthreads();
   const int cl0 = max(cb0, s.dw0) - s.dw0, cl1 = min(cb0 + n, s.dw0 + s.qdw) - s.dw0;  // local output columns [cl0,cl1)
+  if constexpr (REGS) {
+    // every thread finishes its own pairs: in-block sum from the tile + out-of-block sum from its registers (the addition the tile's
+    // read-modify-write did), stored from the registers.  A local column in [cl0,cl1) is a column of the block, so the guard of the
+    // store is the guard of the tile read as well.
+    const bool rowok = i0 + r < s.dimup;
+    const int lc0 = cb0 - s.dw0 + c0;  // local column of pair 0
+    if (wc == 0) {  // natural layout [local column][pitch] (the launcher passes no row-major patches here)
+#pragma unroll
+      for (int it = 0; it < NP; ++it) {
+        const int lc = lc0 + it * cstep;
+        if (it < nlive && lc >= cl0 && lc < cl1 && rowok) {
+          VT a = lds_ld<VT>(tq + it * T * VB);
+          vadd(a, okeep[it]);
+          wt[(int64_t)lc * s.pitch + i0 + r] = a;
+        }
+      }
+      return;
+    }
+    // blocked scratch, column-major patches: pair (column lc, row r) is element (lc mod wc)*R + r of the patch of group lc / wc, and
+    // lc0 - c0's group is aligned to the mapping -- the addresses are the ones of the sweeps below with g0 = that group (it lies before
+    // the slab when the slab's edge cuts the block: nothing is stored there)
+    wc &= 0xFF;
+    const int lw = 31 - __clz(wc);
+    const int gb = (lc0 - (tid >> LR)) >> lw;  // (arithmetic shift of a multiple of wc)
+    const int per = R << lw;
+    const int gstep = T >> (LR + lw);
+    const int rem = tid & (per - 1), gi = tid >> (LR + lw);
+    const uint32_t drows = (uint32_t)((s.dimup + R - 1) & ~(R - 1));
+    const uint32_t so = (uint32_t)gi * (drows * per / R * VB) + (uint32_t)rem * VB;
+    char* __restrict__ dstb = reinterpret_cast<char*>(wt) + ((int64_t)gb * (int64_t)drows + i0) * ((int64_t)VB << lw);
+    const int64_t dstep = (int64_t)gstep * drows * ((int64_t)VB << lw);
+#pragma unroll
+    for (int it = 0; it < NP; ++it) {
+      const int lc = lc0 + it * cstep;
+      if (it < nlive && lc >= cl0 && lc < cl1 && rowok) {
+        VT a = lds_ld<VT>(tq + it * T * VB);
+        vadd(a, okeep[it]);
+        store_stream(reinterpret_cast<VT*>(dstb + it * dstep + so), a);  // (streaming: see below)
+      }
+    }
+    return;
+  }
   if (wc == 0) {
     // natural layout [local column][pitch], lanes along the R rows (row-panel product of the all-to-all exchange:
     // 1/P of the data, so the short strided write runs do not matter)
@@ -1143,34 +1222,73 @@ hipError_t launch_up(const DevSector& s, const DevTiles& t, int lds_bytes, int t
   return launch_up_lz<C, 0, VT>(s, t, lds_bytes, threads, norb1, wc, v, wt, hv, LzEpilogue(), st);
 }
 
-template <int R, int NP, typename VT>
-hipError_t launch_dw_np(const DevSector& s, const DevTiles& t, int lds_bytes, int threads, int wc, const VT* v, VT* hv,
-                        hipStream_t st) {
+// Which instantiations of pass B are built with the out-of-block sums in registers (hxv_pass_dw, ORD 1): up to four pairs per thread
+// (eight would be 32 registers of sums), and only where the kernel stays within the 64 vector registers of two 1024-thread workgroups
+// per CU without a spill (-Rpass-analysis=kernel-resource-usage; the table is in LABNOTES.md)
+template <int R, int NP, bool REAL, typename VT>
+constexpr bool dw_regs_built() {
+  constexpr bool cplx = std::is_same<VT, double2>::value;
+  if (NP > 4) return false;
+  if (cplx && R == 8 && (NP == 4 || (NP == 2 && !REAL))) return false;  // 8 - 12 spilled vector registers (NP 4), 2 - 3 (NP 2, complex H)
+  if (cplx && R == 2 && NP == 4 && !REAL) return false;                 // 2 spilled with the half-size in-block table
+  return true;
+}
+
+template <int R, int NP, bool REAL, typename VT, int ORD>
+auto dw_kernel(bool p16) -> void (*)(DevSector, DevTiles, const VT*, VT*, int, int, int) {
+  if constexpr (ORD == 0 || dw_regs_built<R, NP, REAL, VT>())
+    return p16 ? hxv_pass_dw<R, NP, REAL, true, VT, ORD> : hxv_pass_dw<R, NP, REAL, false, VT, ORD>;
+  else
+    return nullptr;
+}
+
+template <int R, int NP, int ORD, typename VT>
+hipError_t launch_dw_ord(const DevSector& s, const DevTiles& t, int lds_bytes, int threads, int wc, const VT* v, VT* hv,
+                         hipStream_t st) {
   const int ngroups = (s.dimup + R - 1) / R;
   const int gpx = (ngroups + 7) / 8;
   const int64_t nwg = (int64_t)((gpx + 1) & ~1) * 8 * t.nblocks;  // (an even number of row groups per XCD: DevTiles::pair_rows)
   void (*kern)(DevSector, DevTiles, const VT*, VT*, int, int, int);
   const bool p16 = t.ell16 != nullptr;  // (the half-size in-block table exists: blocks <= 1024 columns, <= 64 signed coefficients)
   if constexpr (std::is_same<VT, double>::value)
-    kern = p16 ? hxv_pass_dw<R, NP, true, true, double> : hxv_pass_dw<R, NP, true, false, double>;
+    kern = dw_kernel<R, NP, true, double, ORD>(p16);
   else if (s.real_h)
-    kern = p16 ? hxv_pass_dw<R, NP, true, true, double2> : hxv_pass_dw<R, NP, true, false, double2>;
+    kern = dw_kernel<R, NP, true, double2, ORD>(p16);
   else
-    kern = p16 ? hxv_pass_dw<R, NP, false, true, double2> : hxv_pass_dw<R, NP, false, false, double2>;
+    kern = dw_kernel<R, NP, false, double2, ORD>(p16);
+  if (!kern) return hipErrorInvalidValue;  // (an order that is not built for this instantiation: launch_dw_np does not ask for it)
   hipError_t e = allow_dynamic_lds((const void*)kern, lds_bytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(threads), (size_t)lds_bytes, st, s, t, v, hv, ngroups, gpx, wc);
   return hipGetLastError();
 }
 
+// The order of pass B's phases for one launch (hxv_pass_dw, ORD).  The register order needs the store's thread-to-pair mapping: natural
+// layout or column-major patches, and room for the up to wc-1 dead column positions in front of a block in the NP sweeps of a workgroup.
+template <int R, int NP, typename VT>
+hipError_t launch_dw_np(const DevSector& s, const DevTiles& t, int max_block, int lds_bytes, int threads, int wc, const VT* v, VT* hv,
+                        hipStream_t st, int* order_ran) {
+  const bool regs_built = std::is_same<VT, double>::value ? dw_regs_built<R, NP, true, VT>()
+                                                          : (s.real_h ? dw_regs_built<R, NP, true, VT>() : dw_regs_built<R, NP, false, VT>());
+  const int wcw = wc & 0xFF;
+  const bool mapped = wc == 0 || (wc & 0x100) != 0;
+  const bool fits = (int64_t)(max_block + (wcw ? wcw - 1 : 0)) * R <= (int64_t)NP * threads;
+  const int ord = (regs_built && mapped && fits && !(t.debug & 8192)) ? 1 : 0;
+  if (order_ran) *order_ran = ord;
+  if constexpr (NP <= 4) {
+    if (ord == 1) return launch_dw_ord<R, NP, 1, VT>(s, t, lds_bytes, threads, wc, v, hv, st);
+  }
+  return launch_dw_ord<R, NP, 0, VT>(s, t, lds_bytes, threads, wc, v, hv, st);
+}
+
 template <int R, typename VT>
 hipError_t launch_dw(const DevSector& s, const DevTiles& t, int max_block, int lds_bytes, int threads, int wc, const VT* v,
-                     VT* hv, hipStream_t st) {
+                     VT* hv, hipStream_t st, int* order_ran) {
   const int np = (max_block * R + threads - 1) / threads;  // <= R because max_block <= threads
-  if (np <= 1) return launch_dw_np<R, 1, VT>(s, t, lds_bytes, threads, wc, v, hv, st);
-  if (np <= 2) return launch_dw_np<R, 2, VT>(s, t, lds_bytes, threads, wc, v, hv, st);
-  if (np <= 4) return launch_dw_np<R, 4, VT>(s, t, lds_bytes, threads, wc, v, hv, st);
-  return launch_dw_np<R, 8, VT>(s, t, lds_bytes, threads, wc, v, hv, st);
+  if (np <= 1) return launch_dw_np<R, 1, VT>(s, t, max_block, lds_bytes, threads, wc, v, hv, st, order_ran);
+  if (np <= 2) return launch_dw_np<R, 2, VT>(s, t, max_block, lds_bytes, threads, wc, v, hv, st, order_ran);
+  if (np <= 4) return launch_dw_np<R, 4, VT>(s, t, max_block, lds_bytes, threads, wc, v, hv, st, order_ran);
+  return launch_dw_np<R, 8, VT>(s, t, max_block, lds_bytes, threads, wc, v, hv, st, order_ran);
 }
 
 std::vector<double2> signed_coefs(const SpinOp& op) {
@@ -1369,15 +1487,15 @@ static hipError_t launch_tiled_vt(const DevSector& s, const TilePlan& plan, cons
         const double2* v2 = reinterpret_cast<const double2*>(v);
         double2* w2 = reinterpret_cast<double2*>(wt);
         if (R == 4)
-          e = launch_dw<2, double2>(sp, td, plan.dw.max_block, lds_b, tb, wc_b, v2, w2, st);
+          e = launch_dw<2, double2>(sp, td, plan.dw.max_block, lds_b, tb, wc_b, v2, w2, st, &plan.dw_order_last);
         else
-          e = launch_dw<4, double2>(sp, td, plan.dw.max_block, lds_b, tb, wc_b, v2, w2, st);
+          e = launch_dw<4, double2>(sp, td, plan.dw.max_block, lds_b, tb, wc_b, v2, w2, st, &plan.dw_order_last);
       }
     }
     if (!dw_pairs) switch (R) {
-        case 2: e = launch_dw<2, VT>(s, td, plan.dw.max_block, lds_b, tb, wc_b, v, wt, st); break;
-        case 4: e = launch_dw<4, VT>(s, td, plan.dw.max_block, lds_b, tb, wc_b, v, wt, st); break;
-        default: e = launch_dw<8, VT>(s, td, plan.dw.max_block, lds_b, tb, wc_b, v, wt, st); break;
+        case 2: e = launch_dw<2, VT>(s, td, plan.dw.max_block, lds_b, tb, wc_b, v, wt, st, &plan.dw_order_last); break;
+        case 4: e = launch_dw<4, VT>(s, td, plan.dw.max_block, lds_b, tb, wc_b, v, wt, st, &plan.dw_order_last); break;
+        default: e = launch_dw<8, VT>(s, td, plan.dw.max_block, lds_b, tb, wc_b, v, wt, st, &plan.dw_order_last); break;
       }
   }
   if (e != hipSuccess) return e;

@@ -59,7 +59,7 @@ struct SpinTiles {
 };
 
 // bits of TileOptions::debug that leave the results bit-identical (DevTiles::debug): the others are timing experiments with wrong results
-constexpr int TILE_DEBUG_EXACT = 4096;
+constexpr int TILE_DEBUG_EXACT = 4096 | 8192;
 
 struct TileOptions {
   int cols_per_tile = 4;      // pass A (up hops): columns per workgroup tile
@@ -88,7 +88,7 @@ struct TileOptions {
   int job_groups = 100; // column groups per job (about: an XCD's groups are cut into equal runs)
   int job_stages = 4;  // depth of the LDS tile ring (clamped to what fits 160 KB)
   int job_debug = 0;   // timing experiments only (JobUp::debug); results are wrong when non-zero
-  int debug = 0;   // timing experiments only (see DevTiles::debug); results are wrong when a bit other than 4096 is set
+  int debug = 0;   // timing experiments only (see DevTiles::debug); results are wrong when a bit other than 4096 and 8192 is set
   int passes = 3;     // bit 0: pass A (diag + up hops), bit 1: pass B (dw hops); timing experiments only
 };
 
@@ -99,6 +99,7 @@ struct TilePlan {
   double2* d_scoef_up = nullptr;  // [2*ncoef+1] signed coefficient tables
   double2* d_scoef_dw = nullptr;
   bool usable = true;             // false: too many distinct amplitudes -> the engine uses kernel 0
+  mutable int dw_order_last = -1;  // phase order of the last pass-B launch (hxv_pass_dw's ORD; -1: none yet): option "pass_b_order_last"
 };
 
 // Optional Lanczos epilogue of pass A (device Lanczos, hxv_lanczos.hip): with x the input vector of the product,

@@ -487,11 +487,15 @@ int hxv_get_diag(const hxv_handle *h, double *diag);
  *
  * 3. TIMING EXPERIMENTS (results are wrong or partial when set; refused unless HXV_EXPERIMENTS=1 is in the environment)
  *   "passes" 1|2|3 [3], "debug" bit mask, "job_debug" bit mask.
- *   One bit of the debug mask leaves the results bit-identical (same gate): 4096, pass B issues its loads also for the pair iterations no
- *   lane of a wave owns (the kernel without the dead-wave skip, for A/B timings).
+ *   Two bits of the debug mask leave the results bit-identical (same gate): 4096, pass B issues its loads also for the pair iterations no
+ *   lane of a wave owns (the kernel without the dead-wave skip, for A/B timings); 8192, pass B runs its phases in the earlier order
+ *   (out-of-block hops after the in-block ones, their sums added into the LDS tile) also where the plan allows the out-of-block sums in
+ *   registers.
  *
  * hxv_get_option additionally reports plan statistics ("tile_bits_up", "nblocks_up", "slots_in_up_x100", "max_outer_up", "job_up_active", ...),
- * driver read-backs ("lanczos_real_last", "eigh_last_full_passes", "eigh_last_local_passes", "eigh_last_search_products",
+ * driver read-backs ("pass_b_order_last": the phase order the last pass-B launch ran, 1 = out-of-block sums in registers, 0 = the earlier
+ * order [eight pairs per thread, row-major scratch patches, a largest block that leaves no room for wt_cols - 1 dead columns, debug bit 8192],
+ * -1 = no launch since the plan was made; "lanczos_real_last", "eigh_last_full_passes", "eigh_last_local_passes", "eigh_last_search_products",
  * "eigh_last_check_products", "slab_copies"; which restart code the last hxv_eigh_lowest ran: "eigh_last_restarts" thick restarts of the search
  * round, "eigh_last_fused_restarts" those whose rotation also measured the residual vector, "eigh_last_fused_first_steps" restart cycles whose
  * first step removed the arrow and measured in one pass) and what the open cost ("open_cache_hit", "open_us_host|plan|upload|total").
