@@ -124,6 +124,10 @@ struct SectorImage {
   struct ObsTables;
   std::shared_ptr<ObsTables> obs;
   std::mutex obs_mu;
+  // the bath-group tables and the work list of the cluster density matrix (hxv_cluster_dm.hip), built on the first hxv_cluster_dm_accumulate
+  struct CdmTables;
+  std::shared_ptr<CdmTables> cdm;
+  std::mutex cdm_mu;
   ~SectorImage();
 };
 // the cache of closed sectors' images (hxv_cache.cpp); an empty key means "do not cache"

@@ -53,6 +53,9 @@ module ED_HAMILTONIAN_GPU_HXV
   !impurity observables of device-resident states (ED_OBSERVABLES.f90 lanc_observables / lanc_local_energy / single-particle density matrix)
   public :: gpu_observables_dev
   public :: gpu_get_observables
+  !cluster reduced density matrix of device-resident states (ED_OBSERVABLES.f90 density_matrix_impurity, cluster_density_matrix)
+  public :: gpu_cluster_dm_dev
+  public :: gpu_get_cluster_dm
 
   !> A vector that lives on the device, in the layout of the sector it was made for.  Opaque: pass it back to the gpu_* routines.
   type :: gpu_vector
@@ -323,10 +326,22 @@ module ED_HAMILTONIAN_GPU_HXV
        real(c_double),intent(in)  :: record(*)
        real(c_double)             :: out(*)
      end function hxv_observables_derive
+     integer(c_int64_t) function hxv_cluster_dm_elems(h) bind(C,name="hxv_cluster_dm_elems")
+       import :: c_int64_t, c_ptr
+       type(c_ptr),value :: h
+     end function hxv_cluster_dm_elems
+     integer(c_int) function hxv_cluster_dm_accumulate(h,d_psi,weight,accumulate,cdm) bind(C,name="hxv_cluster_dm_accumulate")
+       import :: c_int, c_int32_t, c_ptr, c_double
+       type(c_ptr),value        :: h,d_psi
+       real(c_double),value     :: weight
+       integer(c_int32_t),value :: accumulate
+       real(c_double)           :: cdm(*)
+     end function hxv_cluster_dm_accumulate
   end interface
 
   type(c_ptr),save :: handle = c_null_ptr   !one open sector at a time (ED_HAMILTONIAN_COMMON.f90:17-18)
   real(c_double),allocatable,save :: obs_record(:)   !the summed raw record of gpu_observables_dev (include/hxv.h)
+  real(c_double),allocatable,save :: cdm_sum(:)      !the summed matrix of gpu_cluster_dm_dev, (re,im) pairs in cluster_density_matrix's order
 
 contains
 
@@ -1032,5 +1047,44 @@ contains
     spdm=reshape([(cmplx(out(k+2*i-1),out(k+2*i),kind=8),i=1,llo*Nspin*Nspin)],[Nlat,Nlat,Nspin,Nspin,Norb,Norb])
     deallocate(out)
   end subroutine gpu_get_observables
+
+  !> One state of state_list (ED_OBSERVABLES.f90:489-503) into the module's summed cluster density matrix rho_imp = Tr_bath |psi><psi|
+  !! (:514-575, without the eigenvector on the host): vect and peso as gpu_observables_dev takes them.  accumulate=.false. starts a new sum
+  !! (the first state; cluster_density_matrix=zero of :486), .true. adds to it.  On a split sector every rank calls it with its slab and
+  !! holds the global matrix.
+  subroutine gpu_cluster_dm_dev(vect,peso,accumulate)
+    type(gpu_vector),intent(in) :: vect
+    real(8),intent(in)          :: peso
+    logical,intent(in)          :: accumulate
+    integer(c_int64_t)          :: n
+    if(.not.vec_alive(vect))stop "gpu_cluster_dm_dev ERROR: empty vector, or its sector was closed under it (gpu_keep_sector keeps it open)"
+    n=hxv_cluster_dm_elems(vect%sector)
+    if(n<=0)stop "gpu_cluster_dm_dev ERROR: the open sector has no cluster density matrix (Nimp > 5, or no basis maps)"
+    if(accumulate)then
+       if(.not.allocated(cdm_sum))stop "gpu_cluster_dm_dev ERROR: accumulate=.true. before a first state"
+       if(size(cdm_sum,kind=c_int64_t)/=n)stop "gpu_cluster_dm_dev ERROR: the matrix of this sector belongs to another model"
+    else
+       if(allocated(cdm_sum))deallocate(cdm_sum)
+       allocate(cdm_sum(n))
+    endif
+    call check(hxv_cluster_dm_accumulate(vect%sector,vect%d,real(peso,c_double),merge(1_c_int32_t,0_c_int32_t,accumulate),cdm_sum),&
+         "gpu_cluster_dm_dev")
+  end subroutine gpu_cluster_dm_dev
+
+  !> The summed matrix into the reference's cluster_density_matrix(4**Nimp,4**Nimp) (ED_VARS_GLOBAL.f90), as is: element (io,jo),
+  !! io = (IimpUp + 2**Nimp*IimpDw) + 1 (ED_OBSERVABLES.f90:561-566).
+  subroutine gpu_get_cluster_dm(cdm)
+    complex(8),intent(out) :: cdm(:,:)
+    integer                :: i,j,n
+    if(.not.allocated(cdm_sum))stop "gpu_get_cluster_dm ERROR: no state recorded (gpu_cluster_dm_dev)"
+    n=size(cdm,1)
+    if(size(cdm,2)/=n.or.2_c_int64_t*int(n,c_int64_t)*n/=size(cdm_sum,kind=c_int64_t))&
+         stop "gpu_get_cluster_dm ERROR: cdm is not (4**Nimp,4**Nimp) of the recorded sector"
+    do j=1,n
+       do i=1,n
+          cdm(i,j)=cmplx(cdm_sum(2*(i+n*(j-1))-1),cdm_sum(2*(i+n*(j-1))),kind=8)
+       enddo
+    enddo
+  end subroutine gpu_get_cluster_dm
 
 end module ED_HAMILTONIAN_GPU_HXV

@@ -49,6 +49,7 @@ EXPORTS = [
     "hxv_vector_alloc", "hxv_vector_alloc_many", "hxv_vector_free", "hxv_vector_from_host", "hxv_vector_to_host",
     "hxv_sector_cache_clear", "hxv_sector_cache_stats", "hxv_comm_abort", "hxv_comm_library", "hxv_comm_cache_stats", "hxv_comm_cache_clear", "hxv_host_register", "hxv_host_unregister",
     "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
+    "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate",
 ]
 
 _lib = None
@@ -159,6 +160,9 @@ def load_library():
     L.hxv_obs_derived_elems.argtypes = [C.POINTER(_Model)]
     L.hxv_obs_derived_elems.restype = i64
     L.hxv_observables_derive.argtypes = [C.POINTER(_Model), pd, pd]
+    L.hxv_cluster_dm_elems.argtypes = [vp]
+    L.hxv_cluster_dm_elems.restype = i64
+    L.hxv_cluster_dm_accumulate.argtypes = [vp, vp, dbl, i32, pd]
     _lib = L
     return L
 
@@ -863,6 +867,30 @@ class HxvSector:
         torch.cuda.synchronize(psi_device.device)
         _chk(L.hxv_observables_accumulate(self._h, psi_device.data_ptr(), float(weight), int(bool(accumulate)), _p(out, C.c_double)),
              "hxv_observables_accumulate")
+        return out
+
+    def cluster_dm(self, psi_device, weight: float = 1.0, out: np.ndarray | None = None, accumulate: bool = False) -> np.ndarray:
+        """Cluster reduced density matrix rho_imp = Tr_bath |psi><psi| of one device-resident state (include/hxv.h,
+        hxv_cluster_dm_accumulate; the reference's cluster_density_matrix, ED_OBSERVABLES.f90:465-582), weighted by `weight` (the
+        reference's peso): complex128 of shape (4^Nimp, 4^Nimp), element [io, jo] with io = a_up + 2^Nimp a_dw.  psi_device: a device
+        vector of this sector in the padded layout (localElems complex128 elements: this rank's slab on a split sector, collective
+        there).  With accumulate=True the state's matrix is added to `out` (Fortran-ordered, as a previous call returned it)."""
+        import torch
+
+        assert psi_device.is_cuda and psi_device.dtype == torch.complex128 and psi_device.is_contiguous() and psi_device.numel() == self.localElems, \
+            "cluster_dm takes a device vector in the padded layout (localElems elements)"
+        L = load_library()
+        n = L.hxv_cluster_dm_elems(self._h)
+        if n <= 0:
+            raise HxvError("cluster_dm: this handle has no cluster density matrix (built from CSR, a dw panel, or Nimp > 5)")
+        side = int(round((n // 2) ** 0.5))
+        if out is None:
+            assert not accumulate, "accumulate=True needs `out`"
+            out = np.zeros((side, side), dtype=np.complex128, order="F")
+        assert out.dtype == np.complex128 and out.flags.f_contiguous and out.shape == (side, side)
+        torch.cuda.synchronize(psi_device.device)
+        _chk(L.hxv_cluster_dm_accumulate(self._h, psi_device.data_ptr(), float(weight), int(bool(accumulate)),
+                                         C.cast(out.ctypes.data, C.POINTER(C.c_double))), "hxv_cluster_dm_accumulate")
         return out
 
     def time_lanczos(self, nrep: int) -> float:

@@ -76,3 +76,15 @@ def observables(model, states, beta: float | None = None) -> dict:
     for (sec, _, psi), wi in zip(states, w):
         sec.observables_record(psi, weight=wi, out=rec, accumulate=True)
     return derive(model, rec)
+
+
+def cluster_density_matrix(model, states, beta: float | None = None) -> np.ndarray:
+    """The reference's cluster_density_matrix (dm_flag; density_matrix_impurity, ED_OBSERVABLES.f90:465-582) of the whole state list:
+    rho_imp = sum_i peso_i Tr_bath |psi_i><psi_i|, complex (4^Nimp, 4^Nimp), element [io, jo] with io = a_up + 2^Nimp a_dw.  states and
+    beta as in observables(); every state's matrix is computed on the device (HxvSector.cluster_dm) and summed on the host."""
+    w = thermal_weights([e for _, e, _ in states], beta)
+    n = 4 ** (model.Nlat * model.Norb)
+    rho = np.zeros((n, n), dtype=np.complex128, order="F")
+    for (sec, _, psi), wi in zip(states, w):
+        sec.cluster_dm(psi, weight=wi, out=rho, accumulate=True)
+    return rho

@@ -401,6 +401,23 @@ int hxv_observables_accumulate(hxv_handle *h, const void *d_psi, double weight, 
 int64_t hxv_obs_derived_elems(const hxv_model *model);
 int hxv_observables_derive(const hxv_model *model, const double *record, double *out);
 
+/* ---- cluster reduced density matrix of device-resident states ----------------------------------------------------------------
+ * ED_OBSERVABLES.f90 density_matrix_impurity (:465-582): rho_imp = Tr_bath |psi><psi|, the reference's cluster_density_matrix (dm_flag),
+ * without the eigenvector on the host and without sign factors, as the loop body of :533-568 defines it:
+ *   cdm(io,jo) += weight * sum over (b_up,b_dw) of psi(a_up + 2^Nimp b_up, a_dw + 2^Nimp b_dw) * conj(psi(a'_up + 2^Nimp b_up, a'_dw + 2^Nimp b_dw)),
+ *   io = a_up + 2^Nimp a_dw, jo = a'_up + 2^Nimp a'_dw  (0-based; :539-562: impurity bits low, bath bits high).
+ * hxv_cluster_dm_elems: the length of cdm in doubles, 2 * 16^Nimp: complex(8), interleaved, in the reference's Fortran order, element
+ * (io,jo) at 2*(io + 4^Nimp*jo); 0 for handles without basis maps (from CSR), dw panels and Nimp > 5.
+ * hxv_cluster_dm_accumulate: d_psi is a device vector of h (this rank's slab in the padded layout, device row order included; pad rows are
+ * never read).  accumulate == 0 overwrites cdm, otherwise adds weight * (this state's matrix) to it; weight is the reference's peso
+ * (:502-503).  Runs on the handle's stream and returns once the result is on the host.  The same vector on the same handle gives the same
+ * bits on every call (no floating-point atomics).  Split sectors (after hxv_comm_init / _init_local): collective, every rank returns the
+ * GLOBAL matrix (the reference computes it on the MPI master alone, :511), and all ranks fail together.  Errors: HXV_ERR_ARG for NULL
+ * arguments; HXV_ERR_STATE for a handle without basis maps (from CSR, a dw panel) and for a split sector without its communicator;
+ * HXV_ERR_UNSUPPORTED for Nimp > 5 (the dense matrix is 16 MB at Nimp 5 and 268 MB at Nimp 6).                                      */
+int64_t hxv_cluster_dm_elems(const hxv_handle *h);
+int hxv_cluster_dm_accumulate(hxv_handle *h, const void *d_psi, double weight, int32_t accumulate, double *cdm /* host */);
+
 /* ---- device vectors owned by the library --------------------------------------------------------------------------------
  * For host programs without a HIP binding of their own (the Fortran glue): a local vector of the handle's sector in the padded device
  * layout (hxv_localvec_elems() complex elements, zeroed), from the engine's buffer cache.  Such a pointer is what the device drivers take
