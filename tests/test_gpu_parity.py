@@ -191,8 +191,18 @@ def test_full_size_hermiticity_and_linearity(built):
     hz = sec.apply_device(al * x + be * y)
     torch.cuda.synchronize()
     assert (hz - (al * hx + be * hy)).abs().max().item() <= 1e-12 * hz.abs().max().item()
-    # REAL-vector product at the same size: the real part of the complex product (to rounding: the complex product's
-    # pass A runs as pipelined jobs with another summation order; bit for bit against the same kernels), and symmetric
+    # the job kernel of the PLAIN product at this size ("job_up" defaults to 2: pass A runs as jobs for the fused Lanczos product only, so
+    # nothing above went through it) against the one-tile-per-workgroup kernels: the bound of the C4 / C5 tests between kernel families
+    sec.set_option("job_up", 1)
+    assert sec.get_option("job_up_active") == 1
+    hxj = sec.apply_device(x)
+    torch.cuda.synchronize()
+    assert (hxj - hx).abs().max().item() <= 1e-13 * hx.abs().max().item()
+    del hxj, hz
+    sec.set_option("job_up", 2)
+    # REAL-vector product at the same size: the real part of the complex product.  Both run pass A on the one-tile-per-workgroup kernels
+    # (job_up = 2, and 0 below), which do the same operations in the same order on real and on complex vectors: the bound of the first
+    # comparison dates from the time the plain complex product ran as jobs, the second asks for equal bits.  And symmetric.
     xr, yr = x.real.contiguous(), y.real.contiguous()
     hxr = sec.apply_device_real(xr)
     ref_r = sec.apply_device(xr.to(torch.complex128)).real
@@ -377,7 +387,7 @@ def test_real_vector_mode_refused_for_complex_h_and_shards(built):
 
 def test_full_size_c4_complex_hermiticity_and_linearity(built):
     """BASELINE C4 at full size (BHZ 2x2 + 1 bath, Ns=16, Dim = 165 636 900, complex amplitudes, H_up != H_dw):
-    <x|H y> = conj(<y|H x>) and linearity through the complex-coefficient tiled / job kernels, and the tiled
+    <x|H y> = conj(<y|H x>) and linearity through the complex-coefficient tiled kernels, and the tiled
     product against the one-thread-per-element kernel."""
     import torch
     import hxv
@@ -397,7 +407,11 @@ def test_full_size_c4_complex_hermiticity_and_linearity(built):
     hz = sec.apply_device(al * x + be * y)
     torch.cuda.synchronize()
     assert (hz - (al * hx + be * hy)).abs().max().item() <= 1e-12 * hz.abs().max().item()
-    for opt in ("job_up", "kernel"):   # job kernels -> one-tile-per-workgroup kernels -> one thread per element
+    # this plan cannot run pass A as jobs (BHZ blocks have more than the 8 out-of-block partners the job kernel keeps in registers:
+    # max_outer_up > 8), whatever "job_up" says: everything above ran on the one-tile-per-workgroup kernels
+    sec.set_option("job_up", 1)
+    assert sec.get_option("job_up_active") == 0 and sec.get_option("max_outer_up") > 8
+    for opt in ("job_up", "kernel"):   # the same kernels with job_up = 0 (same plan) -> one thread per element
         sec.set_option(opt, 0)
         h2 = sec.apply_device(x)
         torch.cuda.synchronize()
@@ -424,7 +438,7 @@ def _chunked(fn, n, step=1 << 27):
 
 def test_c5_ns18_full_size_single_gpu(built):
     """BASELINE config 5 (Ns=18, sector (9,9), Dim = 2 363 904 400, 37.8 GB per vector) on ONE GPU at full size:
-    tiled/job kernels vs the one-thread-per-element kernel, Hermiticity and linearity (64-bit indexing: Dim > 2^31)."""
+    tiled kernels vs the one-thread-per-element kernel, Hermiticity and linearity (64-bit indexing: Dim > 2^31)."""
     import torch
     import hxv
     from hxv import models
@@ -458,7 +472,8 @@ def test_c5_ns18_full_size_single_gpu(built):
     b = sum(_chunked(lambda s: torch.vdot(y[s], hx[s]).item(), n))
     scale = (sum(_chunked(lambda s: (x[s].abs() ** 2).sum().item(), n)) * sum(_chunked(lambda s: (hy[s].abs() ** 2).sum().item(), n))) ** 0.5
     assert abs(a - b.conjugate()) <= 1e-12 * scale
-    # one-thread-per-element kernel and the one-tile-per-workgroup kernels against the default path, into y's storage
+    # the one-tile-per-workgroup kernels with job_up = 0 and the one-thread-per-element kernel against the default path, into y's storage
+    # (64 up blocks are more than "job_max_blocks" = 32: this plan never runs pass A as jobs, asserted below)
     hmax = max(_chunked(lambda s: hx[s].abs().max().item(), n))
     for opt in ("job_up", "kernel"):
         sec.set_option(opt, 0)
@@ -469,6 +484,7 @@ def test_c5_ns18_full_size_single_gpu(built):
         assert max(_chunked(lambda s: (y[s] - hx[s]).abs().max().item(), n)) <= 1e-13 * hmax, opt
     sec.set_option("kernel", 1)
     sec.set_option("job_up", 1)
+    assert sec.get_option("job_up_active") == 0
     # linearity: z = al x + be (old y is gone: use hx as the second vector) -> H z = al H x + be H hx
     al, be = 0.3 - 1.1j, -0.7 + 0.2j
     sec.apply_device(hx, y)                       # y := H hx
