@@ -314,14 +314,14 @@ static void build_local(orc_sector *s) {
     if (s->hfmode) {
       for (int ilat = 1; ilat <= Nlat; ilat++)
         for (int iorb = 1; iorb <= Norb; iorb++)
-          htmp += -0.5 * s->Uloc[iorb - 1] * (nup[ilat][iorb] + ndw[ilat][iorb]) + 0.25 * s->Uloc[iorb - 1];
+          htmp = htmp - 0.5 * s->Uloc[iorb - 1] * (nup[ilat][iorb] + ndw[ilat][iorb]) + 0.25 * s->Uloc[iorb - 1]; /* (htmp - a) + b, as :67 */
       if (Norb > 1) {
         for (int ilat = 1; ilat <= Nlat; ilat++)
           for (int iorb = 1; iorb <= Norb; iorb++)
             for (int jorb = iorb + 1; jorb <= Norb; jorb++) {
               double nn = nup[ilat][iorb] + ndw[ilat][iorb] + nup[ilat][jorb] + ndw[ilat][jorb];
-              htmp += -0.5 * s->Ust * nn + 0.25 * s->Ust;
-              htmp += -0.5 * (s->Ust - s->Jh) * nn + 0.25 * (s->Ust - s->Jh);
+              htmp = htmp - 0.5 * s->Ust * nn + 0.25 * s->Ust; /* left to right, as :74-75 */
+              htmp = htmp - 0.5 * (s->Ust - s->Jh) * nn + 0.25 * (s->Ust - s->Jh);
             }
       }
     }

@@ -1,6 +1,6 @@
 // Stand-alone tile-plan checker ("plan checker").  No HIP runtime call, no device.
 //
-//   plan_check MODEL nup ndw rank nranks exchange [--panel ROWS] [--dump DIR] [name=value ...] [/ name=value ...] ...
+//   plan_check MODEL nup ndw rank nranks exchange [--panel ROWS] [--dump DIR [--dump-diag]] [name=value ...] [/ name=value ...] ...
 //
 // MODEL is a file with the fields of hxv_model in the array order of HxvSector._model_struct (tests/test_host_plan_check.py writes it).
 // The sector is built by build_sector_from_model (the halo layout with exchange = 1; the row panel of the all-to-all exchange by
@@ -631,6 +631,13 @@ void dump_sector(const SectorHost& S, const std::string& dir) {
   dump_raw(dir, "map_up.u32", S.map_up.data(), S.map_up.size() * sizeof(uint32_t));
   dump_raw(dir, "map_dw.u32", S.map_dw.data(), S.map_dw.size() * sizeof(uint32_t));
 }
+// --dump-diag: what hxv_get_diag returns, this rank's DimUp x qdw elements (one double per element: small sectors only)
+void dump_diag(const SectorHost& S, const std::string& dir) {
+  std::vector<double> d((size_t)S.dimup * (size_t)S.qdw);
+  for (int c = 0; c < S.qdw; ++c)
+    for (int i = 0; i < S.dimup; ++i) d[(size_t)i + (size_t)c * S.dimup] = host_diag_element(S, i, c + S.dw0);
+  dump_raw(dir, "diag.f64", d.data(), d.size() * sizeof(double));
+}
 
 // what the kernels and the job predicates see of the sector (hxv_capi.hip, upload_image), without the device pointers
 DevSector host_view(const SectorHost& s) {
@@ -783,7 +790,7 @@ bool check_plan(const SectorHost& S, const std::vector<std::pair<std::string, lo
 
 int main(int argc, char** argv) {
   if (argc < 7) {
-    fprintf(stderr, "usage: plan_check MODEL nup ndw rank nranks exchange [--panel ROWS] [--dump DIR] [name=value ...] [/ name=value ...]\n");
+    fprintf(stderr, "usage: plan_check MODEL nup ndw rank nranks exchange [--panel ROWS] [--dump DIR [--dump-diag]] [name=value ...] [/ name=value ...]\n");
     return 1;
   }
   ModelFile mf;
@@ -792,11 +799,13 @@ int main(int argc, char** argv) {
   REQUIRE(exchange >= 0 && exchange <= 2, "exchange must be 0, 1 or 2");
   int panel = 0;
   std::string dump;
+  bool with_diag = false;
   std::vector<std::vector<std::pair<std::string, long>>> sets(1);
   for (int a = 7; a < argc; ++a) {
     const std::string arg = argv[a];
     if (arg == "--panel" && a + 1 < argc) panel = atoi(argv[++a]);
     else if (arg == "--dump" && a + 1 < argc) dump = argv[++a];
+    else if (arg == "--dump-diag") with_diag = true;
     else if (arg == "/") sets.emplace_back();
     else {
       const size_t eq = arg.find('=');
@@ -810,6 +819,7 @@ int main(int argc, char** argv) {
   if (!e.empty()) fail("build_sector_from_model: " + e);
   if (nranks > 1 && exchange == 1) REQUIRE(main_sector.exchange == 1 && (int)main_sector.halo_ptr.size() == nranks + 1, "the halo layout was not made");
   if (!dump.empty()) dump_sector(main_sector, dump);
+  if (!dump.empty() && with_diag) dump_diag(main_sector, dump);
   if (main_sector.row_order()) check_row_order(main_sector);
   const SectorHost* S = &main_sector;
   if (panel > 0) {
