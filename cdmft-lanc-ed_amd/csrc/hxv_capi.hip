@@ -926,10 +926,7 @@ int64_t hxv_get_option(const hxv_handle* h, const char* name) {
   if (!strcmp(name, "nblocks_dw")) return h->plan.dw.nblocks;
   if (!strcmp(name, "job_up")) return h->plan.opt.job_up;
   if (!strcmp(name, "job_up_active"))
-    return (h->plan.opt.job_up == 1 && h->plan.opt.sort_mode == 0 && job_up_usable(h->dev, h->plan) &&
-            job_up_fits(h->dev, h->plan, false, std::max(h->plan.opt.job_cols, h->plan.opt.wt_cols)))
-               ? 1
-               : 0;
+    return (h->plan.opt.job_up == 1 && job_up_planned(h->dev, h->plan, false, std::max(h->plan.opt.job_cols, h->plan.opt.wt_cols))) ? 1 : 0;
   if (!strcmp(name, "max_outer_up")) return h->plan.up.max_outer;
   if (!strcmp(name, "max_outer_dw")) return h->plan.dw.max_outer;
   return -1;

@@ -147,7 +147,7 @@ void make_vcol(SectorHost& s);
 std::string make_panel_host(const SectorHost& main, int nrows, SectorHost& panel);  // the row panel of the all-to-all exchange
 // needs s.dw (CSR); replaces the all-gather layout by the halo layout (more_*: further referenced columns per column, CSR-like)
 void make_halo(SectorHost& s, const std::vector<int64_t>* more_ptr = nullptr, const std::vector<int32_t>* more_cols = nullptr);
-int default_lowbits_up(int ns, int npart, int ncoef);  // the block bits the DEFAULT plan gives pass A (hxv_tiled.hip): decides the device row order
+int default_lowbits_up(int ns, int npart, int ncoef);  // the block bits the DEFAULT plan gives pass A (hxv_tile_plan.cpp): decides the device row order
 bool row_order_enabled();         // HXV_ROW_ORDER=0 keeps the reference's row order on the device
 std::string row_order_env_key();  // (for the sector-image cache key)
 int default_exchange();            // hxv_set_exchange_default / HXV_EXCHANGE=halo

@@ -15,8 +15,6 @@
 //
 // Reference semantics: ED_HAMILTONIAN_SPARSE_HxV.f90:167-227 (Hv = spH0d.v + spH0ups(1).v + spH0dws(1).v).
 #include <algorithm>
-#include <map>
-#include <mutex>
 #include <type_traits>
 
 #include "hxv_tile_dev.hpp"
@@ -58,28 +56,6 @@ __device__ __forceinline__ double sload_f64(const double* p) {
   asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p) : "memory");
   return r;
 }
-
-struct JobUp {
-  const void* v;       // gathered vector (all-gather layout)
-  const void* wt;      // dw-hop scratch (may be null: no dw part)
-  void* hv;            // local slab
-  int ngroups, gpx;    // column groups of C columns; groups per XCD
-  int gc;              // groups per job
-  int chunks;          // jobs per (XCD, block) = ceil(gpx / gc)
-  int wc;              // wt layout: 0 natural [column][pitch], else column-group-blocked wt[group][row][wc]
-  int ns;              // LDS column stride of a tile (block rows rounded up to 64)
-  int nst;             // ring depth (tiles)
-  int stage_bytes;     // one ring stage: the v tile (and the previous Lanczos vector's tile with the LZ epilogue)
-  int wt_bytes;        // one wt group buffer: block rows x max(wc,1) columns
-  int kin_rows;        // rows of the in-block table (plan k_in)
-  int max_outer;       // most out-of-block slots (row slots + block hops) of any block
-  int debug;           // timing experiments only (option job_debug): 1 no out-of-block gathers, 2 no in-block hops, 4 no compute at all,
-                       // 8 loader skips wt, 16 loader issues nothing, 32 no hv store, 64 nt policy for the wt DMA,
-                       // 128 every gather reads the thread's own row, 256 gathers scattered over the own block
-  const uint32_t* order;  // [nblocks] blocks of a chunk, largest first
-};
-
-constexpr int JOB_WAVES = 16, JOB_LOADER = JOB_WAVES - 1, JOB_MAX_STAGES = 8;
 
 // LZ: 0 plain product, 1 Lanczos epilogue, 2 PAIRED epilogue (real H: Re and Im are two independent real Lanczos vectors, hxv_tiles.hpp)
 // (LDS-DMA destinations are byte offsets: see the note on the host pass's pointer width in hxv_tile_dev.hpp)
@@ -421,35 +397,21 @@ __global__ void __launch_bounds__(1024) hxv_up_job(DevSector s, DevTiles t, JobU
 #pragma clang diagnostic pop
 namespace {
 
-hipError_t allow_lds(const void* kern, int bytes) {
-  static std::mutex mu;
-  static std::map<const void*, int> granted;
-  std::lock_guard<std::mutex> lk(mu);
-  int& g = granted[kern];
-  if (bytes <= g) return hipSuccess;
-  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) g = bytes;
-  return e;
-}
-
-// register-resident tables of a job: up to 24 in-block words and 8 out-of-block slots per row.  Blocks with more slots (BHZ: up
-// to 16) would need a second batch of gathers whose latency nothing covers: measured 5 % slower than one tile per
-// workgroup at C4, so such plans do not run as jobs.
-constexpr int JOB_KIN = 24, JOB_KO = 8;
-
 template <int C, int LZ, int KIN, int KO>
 hipError_t launch_up_job_k(const DevSector& s, const DevTiles& t, const JobUp& jb, int lds_bytes, int64_t nwg, const LzEpilogue& lz,
                            hipStream_t st) {
   const bool norb1 = s.diag.cross.norb == 1;
-  void (*kern)(DevSector, DevTiles, JobUp, LzEpilogue) = nullptr;
-  if constexpr (LZ == 2) {  // the paired epilogue exists for real H only
-    if (!s.real_h) return hipErrorInvalidValue;
-    kern = norb1 ? hxv_up_job<C, true, true, 2, KIN, KO, double2> : hxv_up_job<C, true, false, 2, KIN, KO, double2>;
-  } else if (s.real_h)
-    kern = norb1 ? hxv_up_job<C, true, true, LZ, KIN, KO, double2> : hxv_up_job<C, true, false, LZ, KIN, KO, double2>;
-  else
-    kern = norb1 ? hxv_up_job<C, false, true, LZ, KIN, KO, double2> : hxv_up_job<C, false, false, LZ, KIN, KO, double2>;
-  hipError_t e = allow_lds((const void*)kern, lds_bytes);
+  using Kern = void (*)(DevSector, DevTiles, JobUp, LzEpilogue);
+  if (LZ == 2 && !s.real_h) return hipErrorInvalidValue;  // the paired epilogue exists for real H only
+  const Kern kern = with_bools(
+      [](auto real, auto n1) -> Kern {
+        if constexpr (LZ == 2 && !decltype(real)::value)
+          return nullptr;
+        else
+          return hxv_up_job<C, decltype(real)::value, decltype(n1)::value, LZ, KIN, KO, double2>;
+      },
+      s.real_h != 0, norb1);
+  hipError_t e = allow_dynamic_lds((const void*)kern, lds_bytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64 * JOB_WAVES), (size_t)lds_bytes, st, s, t, jb, lz);
   return hipGetLastError();
@@ -465,51 +427,6 @@ hipError_t launch_up_job_c(const DevSector& s, const DevTiles& t, const JobUp& j
 }
 
 }  // namespace
-
-bool job_up_usable(const DevSector& s, const TilePlan& plan) {
-  const SpinTiles& u = plan.up;
-  return plan.usable && s.diag.mode == 0 && u.max_block <= 64 * JOB_LOADER && u.k_in <= JOB_KIN && u.max_outer <= JOB_KO &&
-         u.d_order != nullptr && s.dimup < 65536 &&  // (packed out-of-block words: hxv_up_job)
-         u.nblocks <= plan.opt.job_max_blocks && plan.opt.job_cols == 1;
-}
-
-static void job_up_geometry(const DevSector& s, const TilePlan& plan, bool lz_xm, int wc, JobUp& jb, int& lds_bytes, int64_t& nwg) {
-  const int C = plan.opt.job_cols;
-  jb.ngroups = (s.qdw + C - 1) / C;
-  jb.gpx = (jb.ngroups + 7) / 8;
-  jb.gc = std::max(1, plan.opt.job_groups);
-  jb.chunks = std::max(1, (jb.gpx + jb.gc / 2) / jb.gc);  // about job_groups groups per job, all jobs of an XCD equally long
-  jb.ns = (plan.up.max_block + 63) & ~63;
-  jb.stage_bytes = (1 + (lz_xm ? 1 : 0)) * C * jb.ns * 16;
-  jb.wt_bytes = jb.ns * std::max(wc, 1) * 16;
-  const int tab = (((2 * plan.ncoef_up + 1) * 16 + 255) & ~255) + 256;  // coefficients, loader bookkeeping words
-  jb.nst = std::min(std::min(plan.opt.job_stages, JOB_MAX_STAGES), (160 * 1024 - tab - 2 * jb.wt_bytes) / jb.stage_bytes);
-  lds_bytes = jb.nst * jb.stage_bytes + 2 * jb.wt_bytes + tab;
-  jb.kin_rows = std::min(plan.up.k_in, (plan.up.k_in_real + 3) & ~3);
-  jb.max_outer = plan.up.max_outer;
-  jb.debug = plan.opt.job_debug;
-  jb.order = plan.up.d_order;
-  nwg = (int64_t)8 * jb.chunks * plan.up.nblocks;
-}
-
-int64_t job_up_workgroups(const DevSector& s, const TilePlan& plan) {
-  JobUp jb{};
-  int lds = 0;
-  int64_t nwg = 0;
-  job_up_geometry(s, plan, false, 0, jb, lds, nwg);
-  return nwg;
-}
-
-bool job_up_fits(const DevSector& s, const TilePlan& plan, bool lz, int wc) {
-  // (the Lanczos epilogue streams the previous vector's tile as well: decided for the worst case so that the choice of
-  //  kernel -- and the number of per-workgroup partial sums -- does not change from one iteration to the next)
-  if (wc > 0 && wc % plan.opt.job_cols != 0) return false;
-  JobUp jb{};
-  int lds = 0;
-  int64_t nwg = 0;
-  job_up_geometry(s, plan, lz, wc, jb, lds, nwg);
-  return jb.nst >= 2;
-}
 
 hipError_t launch_up_job(const DevSector& s, const TilePlan& plan, const DevTiles& tu, int wc, const double2* v, const double2* wt, double2* hv,
                          const LzEpilogue* lz, hipStream_t st) {

@@ -1,5 +1,7 @@
 // Device-side pieces shared by the tiled kernels (hxv_tiled.hip) and the pipelined job kernels (hxv_jobs.hip).
 #pragma once
+#include <type_traits>
+
 #include "hxv_device.hpp"
 #include "hxv_tiles.hpp"
 
@@ -45,7 +47,21 @@ struct DevTiles {
   int nwtr;
 };
 
-constexpr int HOP_CHUNK = 8;
+// The kernels' `wc` argument, the layout of the dw-hop scratch wt.  Bits 0-7: columns per group (0: natural layout [column][pitch]).
+// Pass B, bit 8: the R x wc patches of a group are column-major.  Pass A, bits 8 and up: rows of a column-major patch (0: row-major).
+constexpr int wc_pass_b(int width, bool colmajor) { return width | (colmajor ? 0x100 : 0); }
+constexpr int wc_pass_a(int width, int patch_rows) { return width | (patch_rows << 8); }
+
+// host-side launch helpers (hxv_tiled.hip)
+hipError_t allow_dynamic_lds(const void* kern, int bytes);
+// f(std::bool_constant<b>()...): run-time bools into the template arguments of a kernel
+template <typename F>
+auto with_bools(F&& f) { return f(); }
+template <typename F, typename... B>
+auto with_bools(F&& f, bool b, B... rest) {
+  return b ? with_bools([&](auto... c) { return f(std::true_type(), c...); }, rest...)
+           : with_bools([&](auto... c) { return f(std::false_type(), c...); }, rest...);
+}
 
 // Non-temporal (streaming) accesses.  Measured: SLOWER than plain ones for loads (pass A's wt read: +7 %) and for short
 // strided store segments (R*16-byte column segments of a natural-layout vector: they defeat L2 write combining, see
@@ -64,8 +80,6 @@ __device__ __forceinline__ void store_stream(double2* p, double2 a) {
 }
 
 __device__ __forceinline__ void store_stream(double* p, double a) { __builtin_nontemporal_store(a, p); }
-
-constexpr uint32_t TILE_OFF_MASK = (1u << TILE_COEF_SHIFT) - 1u;
 
 // LDS by byte offset (a kernel's dynamic LDS starts at 0 when it declares no static LDS): addressing through the
 // extern __shared__ symbol costs one vector add per access that the compiler cannot fold.

@@ -14,6 +14,8 @@ namespace hxv {
 //                bounds and adds nothing, so the hop loops carry no per-lane branch.
 constexpr int TILE_COEF_SHIFT = 20;
 constexpr int TILE_MAX_COEF = 255;  // 2*255+1 signed entries fit the LDS table comfortably
+constexpr uint32_t TILE_OFF_MASK = (1u << TILE_COEF_SHIFT) - 1u;
+constexpr int HOP_CHUNK = 8;  // table rows a thread of the tile kernels fetches at once (k_in, k_out are multiples)
 
 // Prefix-block decomposition of one spin sector.  States that share their high (ns-lowbits)
 // bits are contiguous in the sorted basis (ED_SETUP.f90:748-773 orders by integer value) and
@@ -126,12 +128,47 @@ struct PlanUploader {
   std::function<hipError_t(const std::vector<double2>&, double2**)> d2;
 };
 std::string make_tile_plan(const SectorHost& s, TilePlan& plan, const PlanUploader& up);
-// job kernels (hxv_jobs.hip)
+// job kernels (hxv_jobs.hip; their geometry and the decision to run them: hxv_tile_plan.cpp)
 struct DevTiles;
 struct WtRange;
+struct JobUp {
+  const void* v;       // gathered vector (all-gather layout)
+  const void* wt;      // dw-hop scratch (may be null: no dw part)
+  void* hv;            // local slab
+  int ngroups, gpx;    // column groups of C columns; groups per XCD
+  int gc;              // groups per job
+  int chunks;          // jobs per (XCD, block) = ceil(gpx / gc)
+  int wc;              // wt layout: 0 natural [column][pitch], else column-group-blocked wt[group][row][wc]
+  int ns;              // LDS column stride of a tile (block rows rounded up to 64)
+  int nst;             // ring depth (tiles)
+  int stage_bytes;     // one ring stage: the v tile (and the previous Lanczos vector's tile with the LZ epilogue)
+  int wt_bytes;        // one wt group buffer: block rows x max(wc,1) columns
+  int kin_rows;        // rows of the in-block table (plan k_in)
+  int max_outer;       // most out-of-block slots (row slots + block hops) of any block
+  int debug;           // timing experiments only (option job_debug): 1 no out-of-block gathers, 2 no in-block hops, 4 no compute at all,
+                       // 8 loader skips wt, 16 loader issues nothing, 32 no hv store, 64 nt policy for the wt DMA,
+                       // 128 every gather reads the thread's own row, 256 gathers scattered over the own block
+  const uint32_t* order;  // [nblocks] blocks of a chunk, largest first
+};
+
+constexpr int JOB_WAVES = 16, JOB_LOADER = JOB_WAVES - 1, JOB_MAX_STAGES = 8;
+// register-resident tables of a job: up to 24 in-block words and 8 out-of-block slots per row.  Blocks with more slots (BHZ: up
+// to 16) would need a second batch of gathers whose latency nothing covers: measured 5 % slower than one tile per
+// workgroup at C4, so such plans do not run as jobs.
+constexpr int JOB_KIN = 24, JOB_KO = 8;
+
 bool job_up_usable(const DevSector& s, const TilePlan& plan);
+void job_up_geometry(const DevSector& s, const TilePlan& plan, bool lz_xm, int wc, JobUp& jb, int& lds_bytes, int64_t& nwg);
 int64_t job_up_workgroups(const DevSector& s, const TilePlan& plan);
 bool job_up_fits(const DevSector& s, const TilePlan& plan, bool lz, int wc);
+bool job_up_planned(const DevSector& s, const TilePlan& plan, bool lz, int wc);
+// does pass A of this product run as jobs?  wc_out: the scratch group width it then uses
+bool use_job_up(const DevSector& s, const TilePlan& plan, bool real_vec, bool lz, bool wt_natural, int* wc_out = nullptr);
+// tile shapes of the launcher: columns of pass A, rows of pass B, scratch group width (real vectors: twice the complex ones)
+int real_cols(const TilePlan& plan);
+int cplx_cols(const TilePlan& plan);
+int real_rows(const TilePlan& plan);
+int real_wc(const TilePlan& plan);
 hipError_t launch_up_job(const DevSector& s, const TilePlan& plan, const DevTiles& tu, int wc, const double2* v, const double2* wt, double2* hv,
                          const LzEpilogue* lz, hipStream_t st);
 // wtr / nwtr (with only_pass = 1, wt_natural): the dw part handed over in row ranges (WtRange, hxv_tile_dev.hpp) instead of one array;

@@ -31,11 +31,13 @@ using namespace hxv;
 
 namespace {
 
-// what the kernels hard-code (hxv_tile_dev.hpp, hxv_jobs.hip): restated, because this file must stay host-only
+// what the kernels hard-code (hxv_tiles.hpp): restated, the checker uses no name of the builder's, and held equal to the header's
 constexpr int K_HOP_CHUNK = 8;                                  // table rows a thread fetches at once
 constexpr uint32_t K_OFFM = (1u << TILE_COEF_SHIFT) - 1u;       // offset field of a 32-bit table word
 constexpr int K_JOB_KIN = 24, K_JOB_KO = 8, K_JOB_LOADER = 15, K_JOB_MAX_STAGES = 8;
 constexpr int K_LDS_BYTES = 160 * 1024;
+static_assert(K_HOP_CHUNK == HOP_CHUNK && K_OFFM == TILE_OFF_MASK, "the tile kernels' constants changed");
+static_assert(K_JOB_KIN == JOB_KIN && K_JOB_KO == JOB_KO && K_JOB_LOADER == JOB_LOADER && K_JOB_MAX_STAGES == JOB_MAX_STAGES, "the job kernel's constants changed");
 
 std::string fmt(const char* f, ...) {
   char buf[1024];

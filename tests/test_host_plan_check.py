@@ -80,6 +80,17 @@ def checker(built):
     return built.build_plan_check()
 
 
+def test_checker_is_built_from_host_sources_only(built):
+    """The checker's source list names C++ files only, the plan builder among them, and the plan builder holds no device code: neither
+    __global__ nor __device__ appears in hxv_tile_plan.cpp."""
+    names = [s.name for s in built.PLAN_CHECK_SOURCES]
+    assert names and all(n.endswith(".cpp") for n in names), names
+    plan = [s for s in built.PLAN_CHECK_SOURCES if s.name == "hxv_tile_plan.cpp"]
+    assert len(plan) == 1, names
+    text = plan[0].read_text()
+    assert "__global__" not in text and "__device__" not in text
+
+
 # ---- the named shapes --------------------------------------------------------------------------------------------------------------------
 def _full_size(key):
     from hxv import models
