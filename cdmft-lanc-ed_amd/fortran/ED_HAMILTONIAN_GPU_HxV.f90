@@ -36,6 +36,7 @@ module ED_HAMILTONIAN_GPU_HXV
   public :: gpu_sp_eigh_dev
   public :: gpu_keep_sector
   public :: gpu_apply_ladder
+  public :: gpu_twin_vector
   public :: gpu_sp_lanc_tridiag_dev
   public :: gpu_sp_lanc_tridiag_pair_dev
   public :: gpu_vector_to_host
@@ -297,6 +298,10 @@ module ED_HAMILTONIAN_GPU_HXV
        real(c_double),value     :: coef_re,coef_im
        real(c_double)           :: norm2
      end function hxv_apply_ladder_axpy
+     integer(c_int) function hxv_twin_vector(from,to,d_psi,d_out) bind(C,name="hxv_twin_vector")
+       import :: c_int, c_ptr
+       type(c_ptr),value        :: from,to,d_psi,d_out
+     end function hxv_twin_vector
      integer(c_int) function hxv_get_stats(h,st) bind(C,name="hxv_get_stats")
        import :: c_int, c_ptr, hxv_stats
        type(c_ptr),value :: h
@@ -760,6 +765,23 @@ contains
     call check(hxv_apply_ladder_axpy(psi%sector,handle,int(ipos-1,c_int32_t),int(ispin-1,c_int32_t),cr,dble(cf),aimag(cf),acc,psi%d,out%d,norm2),&
          "gpu_apply_ladder")
   end subroutine gpu_apply_ladder
+
+  !> out = psi as a vector of its twin sector: from psi's sector (nup,ndw) into the OPEN sector, which must be (ndw,nup).  The twin branch of
+  !! es_return_cvector (ED_EIGENSPACE.f90:485-494, vector(i)=twin%cvec(Order(i)), Order of ED_SETUP.f90:854-898) on the device: with ed_twin
+  !! the state found in one sector of a pair serves the other one without a Dim-sized PCIe transfer.  No sign; an eigenstate of the open
+  !! sector for spin-symmetric models only (the reference warns for Nspin>1).  Split sectors are refused by the engine.
+  subroutine gpu_twin_vector(psi,out)
+    type(gpu_vector),intent(in)    :: psi
+    type(gpu_vector),intent(inout) :: out
+    if(.not.c_associated(handle))stop "gpu_twin_vector ERROR: Hsector NOT set (build the target sector first)"
+    if(.not.vec_alive(psi))stop "gpu_twin_vector ERROR: empty source vector, or its sector was closed under it (gpu_keep_sector keeps it open)"
+    if(.not.c_associated(out%d))then
+       call check(hxv_vector_alloc(handle,out%d),"gpu_twin_vector")
+       call vec_born(out,out%d,.false.)
+    endif
+    if(out%sector_id/=handle_serial)stop "gpu_twin_vector ERROR: the target vector does not belong to the open sector"
+    call check(hxv_twin_vector(psi%sector,handle,psi%d,out%d),"gpu_twin_vector")
+  end subroutine gpu_twin_vector
 
   !> sp_lanc_tridiag (ED_GF_NORMAL.f90:215) from a start vector that is on the device already (normalised by the engine).
   subroutine gpu_sp_lanc_tridiag_dev(vin,alanc,blanc,threshold)

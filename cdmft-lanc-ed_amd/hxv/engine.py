@@ -49,7 +49,7 @@ EXPORTS = [
     "hxv_vector_alloc", "hxv_vector_alloc_many", "hxv_vector_free", "hxv_vector_from_host", "hxv_vector_to_host",
     "hxv_sector_cache_clear", "hxv_sector_cache_stats", "hxv_comm_abort", "hxv_comm_library", "hxv_comm_cache_stats", "hxv_comm_cache_clear", "hxv_host_register", "hxv_host_unregister",
     "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
-    "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate",
+    "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_twin_vector",
 ]
 
 _lib = None
@@ -163,6 +163,7 @@ def load_library():
     L.hxv_cluster_dm_elems.argtypes = [vp]
     L.hxv_cluster_dm_elems.restype = i64
     L.hxv_cluster_dm_accumulate.argtypes = [vp, vp, dbl, i32, pd]
+    L.hxv_twin_vector.argtypes = [vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -848,6 +849,22 @@ class HxvSector:
         _chk(load_library().hxv_apply_ladder_axpy(self._h, to._h, orbital, spin, int(bool(create)), cf.real, cf.imag, int(accumulate),
                                                   psi.data_ptr(), out.data_ptr(), C.byref(n2)), "hxv_apply_ladder_axpy")
         return (to.unpad(out) if (contiguous and not accumulate) else out), n2.value
+
+    def twin_vector(self, to: "HxvSector", psi, out=None):
+        """The state psi of this sector (nup,ndw) as a vector of its twin sector `to` = (ndw,nup) (include/hxv.h, hxv_twin_vector; the twin
+        branch of the reference's es_return_cvector, ED_EIGENSPACE.f90:485-494): the transpose of the amplitude matrix, without a sign, on
+        the device.  psi, out: device vectors in the padded layout (localElems complex128 elements of this sector / of `to`); `out` is
+        allocated when not given, every element of it is written.  to is self is allowed where nup == ndw.  Split sectors are refused."""
+        import torch
+
+        assert psi.is_cuda and psi.dtype == torch.complex128 and psi.is_contiguous() and psi.numel() == self.localElems, \
+            "twin_vector takes a device vector in the padded layout (localElems elements)"
+        if out is None:
+            out = torch.empty(to.localElems, dtype=torch.complex128, device=psi.device)
+        assert out.is_cuda and out.dtype == torch.complex128 and out.is_contiguous() and out.numel() == to.localElems
+        torch.cuda.synchronize(psi.device)
+        _chk(load_library().hxv_twin_vector(self._h, to._h, psi.data_ptr(), out.data_ptr()), "hxv_twin_vector")
+        return out
 
     def observables_record(self, psi_device, weight: float = 1.0, out: np.ndarray | None = None, accumulate: bool = False) -> np.ndarray:
         """Raw impurity-observables record of one device-resident state (include/hxv.h, hxv_observables_accumulate): W, R_up, R_dw as

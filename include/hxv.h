@@ -370,6 +370,27 @@ int hxv_apply_ladder(hxv_handle *from, hxv_handle *to, int32_t orbital, int32_t 
 int hxv_apply_ladder_axpy(hxv_handle *from, hxv_handle *to, int32_t orbital, int32_t spin, int32_t create, double coef_re,
                           double coef_im, int32_t accumulate, const void *d_psi, void *d_out, double *norm2);
 
+/* ---- twin-sector eigenstates (ed_twin) --------------------------------------------------------------------------------------
+ * With ed_twin the reference solves one sector of every pair A = (nup,ndw), B = (ndw,nup) (ED_SETUP.f90:353-362), stores each eigenstate
+ * once with a twin link (ED_DIAG.f90:84,231) and lets every consumer rebuild B's vector through es_return_cvector,
+ * vector(i) = twin%cvec(Order(i)) (ED_EIGENSPACE.f90:485-494), Order = twin_sector_order (ED_SETUP.f90:854-898): the argsort of the
+ * spin-flipped Fock states, i.e. the transpose of the DimUp x DimDw amplitude matrix,
+ *     v_B[idw_A + iup_A*DimDw_A] = v_A[iup_A + idw_A*DimUp_A].
+ * hxv_twin_vector does that on the device: d_psi is a device vector of `from` (sector A), d_out one of `to` (sector B = (ndw,nup) of the
+ * same Ns), both in the padded device layout; pad rows of d_psi are never read, every element of d_out is written, its pad rows as zero.
+ * It runs on `to`'s stream and returns when done.  from == to with nup == ndw is allowed: the spin-flip map on that sector.
+ * THE MAP CARRIES NO SIGN, as in the reference.  It is data movement and is defined for any model, but the result is an eigenstate of B
+ * only for spin-symmetric models (H_up = H_dw: H_B = T H_A T^t exactly); the reference only warns for Nspin > 1, and so does this comment:
+ * nothing is refused on those grounds.
+ * DEVICE ROW ORDER: each sector's own order and basis signs apply on its side,
+ *     d_out[kB*pitch_B + rB] = sB[rB] * sA[rA] * d_psi[kA*pitch_A + rA],   kB = iperm_A[rA],  kA = iperm_B[rB]
+ * (rA, rB device rows; iperm: device row -> reference row, the inverse of hxv_row_order's perm; s: the basis sign of a device row), so the
+ * result is what hxv_vector_to_host / transpose / hxv_vector_from_host would give, bit for bit, whether none, one or both sectors have an order.
+ * Errors: HXV_ERR_ARG for a NULL argument, handles on different devices, d_out == d_psi, or `to` not the sector (ndw,nup) of `from` with
+ * the same Ns; HXV_ERR_STATE for handles without basis maps (from CSR, dw panels); HXV_ERR_UNSUPPORTED when either handle is split
+ * (nranks > 1) or bound to a communicator: the twin of a DimDw split is a DimUp split, which needs an all-to-all -- OUT OF SCOPE here.  */
+int hxv_twin_vector(hxv_handle *from, hxv_handle *to, const void *d_psi, void *d_out);
+
 /* ---- impurity observables of device-resident states --------------------------------------------------------------------------
  * ED_OBSERVABLES.f90 lanc_observables (:94-236), lanc_local_energy (:246-452) and the single-particle density matrix of
  * density_matrix_impurity (:609-686), without the eigenvector on the host.  The impurity orbitals are the low Nimp = Nlat*Norb bits of
