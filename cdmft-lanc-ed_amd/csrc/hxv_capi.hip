@@ -361,6 +361,8 @@ int hxv_destroy(hxv_handle* h) {
     if (e) (void)hipEventDestroy(e);
   for (auto e : h->ov_ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto e : h->tw_ev)
+    if (e) (void)hipEventDestroy(e);
   if (h->stream2) (void)hipStreamDestroy(h->stream2);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -874,6 +876,10 @@ int64_t hxv_get_option(const hxv_handle* h, const char* name) {
   if (!strcmp(name, "exchange_overlap")) return h->a2a_overlap;
   if (!strcmp(name, "kernel")) return h->kernel;
   if (!strcmp(name, "time_kernels_overlapped_us")) return h->last_overlapped_us;
+  // the last split hxv_twin_vector INTO this handle, by HIP events on its stream (-1: none yet): pack kernel, exchange, unpack kernel
+  if (!strcmp(name, "twin_last_pack_us")) return h->twin_last_us[0];
+  if (!strcmp(name, "twin_last_exchange_us")) return h->twin_last_us[1];
+  if (!strcmp(name, "twin_last_unpack_us")) return h->twin_last_us[2];
   if (!strcmp(name, "tile_bits_up")) return h->plan.up.lowbits;
   if (!strcmp(name, "tile_bits_dw")) return h->plan.dw.lowbits;
   if (!strcmp(name, "real_dw_pairs")) return h->plan.opt.real_dw_pairs;

@@ -225,6 +225,8 @@ struct hxv_handle {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t kt_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // hxv_time_apply_slab: events around the kernels of a slab product (two regions in exchange mode 2; [4], [5]: pass A on the second stream of its overlapped form)
   int kt_on = 0;
+  hipEvent_t tw_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // split hxv_twin_vector into this handle: before pack / after pack / after the exchange / after unpack (created on first use)
+  int64_t twin_last_us[3] = {-1, -1, -1};  // ... and what the three phases of the last such call took on the stream, microseconds (get_option "twin_last_*_us")
   int64_t last_overlapped_us = 0;  // last hxv_time_apply_slab: mean time of the kernels that ran on the second stream beside the exchange (overlapped mode 2), microseconds
 
   template <typename T>

@@ -143,6 +143,8 @@ std::string build_sector_from_csr(int dimup, int dimdw, const int64_t* up_rp, co
                                   int nranks, SectorHost& out);
 std::string build_ell(SpinOp& op);
 void dw_split(int dimdw, int rank, int nranks, int& qdw, int& dw0);
+// elements per peer of the split twin-sector map's one exchange (hxv_twin.hip); false: bad arguments
+bool twin_split_plan(int dimup_a, int dimdw_a, int rank, int nranks, int64_t* send_counts, int64_t* recv_counts);
 void make_vcol(SectorHost& s);
 std::string make_panel_host(const SectorHost& main, int nrows, SectorHost& panel);  // the row panel of the all-to-all exchange
 // needs s.dw (CSR); replaces the all-gather layout by the halo layout (more_*: further referenced columns per column, CSR-like)

@@ -308,6 +308,26 @@ void dw_split(int dimdw, int rank, int nranks, int& qdw, int& dw0) {
   dw0 = rank * q + std::min(rank, rem);
 }
 
+// The plan of the split twin-sector map (include/hxv.h: hxv_twin_split_plan, hxv_twin_vector): A = (nup,ndw) is split along DimDw_A, its
+// twin B along DimDw_B = DimUp_A, both by dw_split.  The block rank p sends to rank q is [q's columns of B = reference up-rows of A] x
+// [p's columns of A], the columns of A fastest, every block row padded to a multiple of 8 elements (128 bytes): qdw_B(q) *
+// roundup8(qdw_A(p)) elements.  Pure arithmetic, the same on every rank: no lists are exchanged.  counts: [nranks], the own entry included.
+bool twin_split_plan(int dimup_a, int dimdw_a, int rank, int nranks, int64_t* send_counts, int64_t* recv_counts) {
+  if (dimup_a < 1 || dimdw_a < 1 || nranks < 1 || rank < 0 || rank >= nranks || nranks > std::min(dimup_a, dimdw_a) || !send_counts || !recv_counts)
+    return false;
+  int qa_me, qb_me, first;
+  dw_split(dimdw_a, rank, nranks, qa_me, first);
+  dw_split(dimup_a, rank, nranks, qb_me, first);
+  for (int p = 0; p < nranks; ++p) {
+    int qa, qb;
+    dw_split(dimdw_a, p, nranks, qa, first);
+    dw_split(dimup_a, p, nranks, qb, first);
+    send_counts[p] = (int64_t)qb * ((qa_me + 7) & ~7);
+    recv_counts[p] = (int64_t)qb_me * ((qa + 7) & ~7);
+  }
+  return true;
+}
+
 // Padded all-gather layout (include/hxv.h, hxv_apply_device): every rank contributes cmax =
 // ceil(DimDw/nranks) column slots, so rank r's slab starts at slot r*cmax; ranks that own one
 // column less (ED_HAMILTONIAN.f90:93-98) leave their last slot unused.

@@ -12,6 +12,24 @@
 //                      ONE column of B (column iperm_A[rA]): both sides move whole 128-byte lines (TW and both pitches are multiples of 8),
 //                      whatever the two row orders are.  Pad rows of d_A are never read; every element of d_B is written, its pad rows with
 //                      zeros (the last tile along rB reaches pitch_B).  Only moves and +-1: the same input gives the same bits.
+//
+// SPLIT SECTORS (both handles rank r of P > 1).  A's slab holds the columns idw in [fa[r], fa[r+1]) of A, B's slab the columns kB in
+// [fb[r], fb[r+1]) of B, i.e. the REFERENCE up-rows of A in that range (DimDw_B = DimUp_A, both split by dw_split): the twin of a DimDw split
+// is a DimUp split, one all-to-all.  The reference gathers the whole vector on the master and permutes there (es_return_cvector_mpi,
+// ED_EIGENSPACE.f90:498-569).  Here: one collective step between two kernels, every number of it from twin_split_plan (hxv_sector.cpp).
+//   block r -> q       [iup in fb[q]..fb[q+1))[idw in fa[r]..fa[r+1)), reference order both ways, idw fastest, rows S(r) = roundup8(qdw_A(r))
+//                      elements apart (every block row starts on a 128-byte line; the stride pads are never written and never read).  The
+//                      blocks towards q = 0..P-1 follow each other in the send buffer, so the row of reference row iup starts at iup * S(r):
+//                      the packer needs no owner table, only its own range [fb[r], fb[r+1)) -- that block goes straight to its place in the
+//                      receive buffer and never through the exchange.
+//   twin_pack_kernel   the tile of twin_transpose_kernel (TW x TW through LDS, the same 33-slot rows and conflict-free accesses).  Loads: runs
+//                      of TW device rows of A inside one local column; stores: runs of TW local columns inside the block row of iup =
+//                      iperm_A[rA].  sA is applied here.  Pad rows of d_psi are never read.
+//   exchange           one comm_sendrecv_cols on `to`'s communicator, offsets in elements (cb = 16 bytes).
+//   twin_unpack_kernel for local column kB and device row rB of B: idw = iperm_B[rB], o = owner of idw in A's split (a table of P+1 firsts,
+//                      counted through with a uniform trip count), d_out = sB * recv_o[kB * S(o) + idw - fa[o]]; stores coalesced along rB,
+//                      rows DimUp_B <= rB < pitch_B written as zero.  No LDS: the gathers of one (kB, block of rB) stay inside P block rows.
+// All element offsets are int64 (a C5 slab is more than 2^31 bytes); both grids loop over their y extent instead of exceeding 65535.
 #include <hip/hip_runtime.h>
 
 #include "hxv_handle.hpp"
@@ -69,9 +87,178 @@ __global__ void __launch_bounds__(TW_THREADS) twin_transpose_kernel(const double
     }
   }
 }
+
+// grid: x = tiles along A's device rows, y = tiles along this rank's qa columns of A (looped when there are more tiles than blocks).
+// send: [DimUp_A rows by reference row][stride]; own: this rank's block in its receive buffer, reference rows [own_lo, own_hi)
+__global__ void __launch_bounds__(TW_THREADS) twin_pack_kernel(const double2* __restrict__ d_a, int dimup_a, int pitch_a, int qa,
+                                                               const int32_t* __restrict__ iperm_a, const uint8_t* __restrict__ sign_a,
+                                                               double2* __restrict__ send, double2* __restrict__ own, int stride, int own_lo, int own_hi) {
+  __shared__ double2 tile[TW * TW_STRIDE];
+  const int tx = threadIdx.x % TW, ty = threadIdx.x / TW;
+  const int ra0 = blockIdx.x * TW;
+  for (int c0 = blockIdx.y * TW; c0 < qa; c0 += gridDim.y * TW) {
+    // load: lane tx along A's rows, one run per (ty, trip) = one local column of A
+    {
+      const int ra = ra0 + tx;
+      const bool in_a = ra < dimup_a;
+      const bool neg_a = in_a && sign_a && sign_a[ra];
+#pragma unroll
+      for (int j = 0; j < TW; j += TW_THREADS / TW) {
+        const int c = c0 + ty + j;
+        double2 x = make_double2(0.0, 0.0);
+        if (in_a && c < qa) {
+          x = d_a[(int64_t)c * pitch_a + ra];
+          if (neg_a) x = make_double2(-x.x, -x.y);
+        }
+        tile[(ty + j) * TW_STRIDE + tx] = x;
+      }
+    }
+    __syncthreads();
+    // store: lane tx along the local columns, one run per (ty, trip) = one row of A = one block row
+    {
+      const int c = c0 + tx;
+      if (c < qa) {
+#pragma unroll
+        for (int j = 0; j < TW; j += TW_THREADS / TW) {
+          const int ra = ra0 + ty + j;
+          if (ra < dimup_a) {
+            const int iup = iperm_a ? iperm_a[ra] : ra;
+            double2* dst = (iup >= own_lo && iup < own_hi) ? own + (int64_t)(iup - own_lo) * stride : send + (int64_t)iup * stride;
+            dst[c] = tile[tx * TW_STRIDE + ty + j];
+          }
+        }
+      }
+    }
+    __syncthreads();  // (the next trip overwrites the tile)
+  }
+}
+
+// grid: x = blocks of TW_THREADS device rows of B up to the pitch, y = this rank's qb columns of B (looped beyond the grid limit).
+// tab: [P+1] first column of A per rank, [P+1] element offset of the block from each rank in recv, [P] row stride of that block
+__global__ void __launch_bounds__(TW_THREADS) twin_unpack_kernel(const double2* __restrict__ recv, const int64_t* __restrict__ tab, int nranks,
+                                                                 double2* __restrict__ d_b, int dimup_b, int pitch_b, int qb,
+                                                                 const int32_t* __restrict__ iperm_b, const uint8_t* __restrict__ sign_b) {
+  const int rb = blockIdx.x * TW_THREADS + threadIdx.x;
+  if (rb >= pitch_b) return;
+  const bool in_b = rb < dimup_b;
+  int64_t off = 0, st = 0;
+  bool neg_b = false;
+  if (in_b) {
+    const int64_t idw = iperm_b ? iperm_b[rb] : rb;
+    int o = 0;
+    for (int p = 1; p < nranks; ++p) o += idw >= tab[p] ? 1 : 0;
+    off = tab[nranks + 1 + o] + idw - tab[o];
+    st = tab[2 * nranks + 2 + o];
+    neg_b = sign_b && sign_b[rb];
+  }
+  for (int kb = blockIdx.y; kb < qb; kb += gridDim.y) {
+    double2 x = make_double2(0.0, 0.0);
+    if (in_b) {
+      x = recv[off + (int64_t)kb * st];
+      if (neg_b) x = make_double2(-x.x, -x.y);
+    }
+    d_b[(int64_t)kb * pitch_b + rb] = x;
+  }
+}
+
+// both handles rank r of the same P > 1, `to` bound to a communicator, the pair checked: pack, one exchange, unpack (see the head of the file)
+int twin_vector_split(hxv_handle* from, hxv_handle* to, const void* d_psi, void* d_out) {
+  const SectorHost &a = from->host, &b = to->host;
+  const int P = b.nranks, r = b.rank;
+  std::vector<int64_t> sc(P), rc(P);
+  if (!twin_split_plan(a.dimup, a.dimdw, r, P, sc.data(), rc.data()))
+    return fail(HXV_ERR_STATE, "hxv_twin_vector: no split plan for this pair (nranks > min(DimUp, DimDw))");
+  if (a.qdw < 1 || b.qdw < 1) return fail(HXV_ERR_STATE, "hxv_twin_vector: a rank without columns");
+  // offsets in elements; the own entries keep their place in both buffers (comm_sendrecv_cols skips the own rank)
+  std::vector<int64_t> send_ptr(P + 1, 0), recv_ptr(P + 1, 0), tab(3 * (size_t)P + 2, 0);
+  for (int p = 0; p < P; ++p) {
+    int q, c0;
+    dw_split(a.dimdw, p, P, q, c0);
+    send_ptr[p + 1] = send_ptr[p] + sc[p];
+    recv_ptr[p + 1] = recv_ptr[p] + rc[p];
+    tab[p] = c0;
+    tab[P + 1 + p] = recv_ptr[p];
+    tab[2 * P + 2 + p] = rc[p] / b.qdw;
+  }
+  tab[P] = a.dimdw;
+  tab[2 * P + 1] = recv_ptr[P];
+  const int64_t stride = sc[r] / b.qdw;
+  // what the packer's addressing rests on: the plan's blocks follow each other by reference row, and this handle's slabs are the plan's
+  if (stride < a.qdw || send_ptr[P] != (int64_t)a.dimup * stride || send_ptr[r] != (int64_t)b.dw0 * stride ||
+      rc[r] != sc[r] || tab[r] != a.dw0)
+    return fail(HXV_ERR_STATE, "hxv_twin_vector: the split plan does not match the handles' slabs");
+  HIPCHK(hipSetDevice(to->device));
+  hipStream_t st = to->stream;
+  double2 *d_send = nullptr, *d_recv = nullptr;
+  int64_t* d_tab = nullptr;
+  int rc_local = HXV_OK;
+  hipError_t e1 = pool_alloc(to->device, (size_t)send_ptr[P] * sizeof(double2), (void**)&d_send);
+  hipError_t e2 = pool_alloc(to->device, (size_t)recv_ptr[P] * sizeof(double2), (void**)&d_recv);
+  hipError_t e3 = hipMalloc((void**)&d_tab, tab.size() * sizeof(int64_t));
+  if (e3 == hipSuccess) e3 = hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, st);
+  for (auto& ev : to->tw_ev)
+    if (!ev && e3 == hipSuccess) e3 = hipEventCreate(&ev);
+  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
+    (void)hipGetLastError();
+    rc_local = fail(HXV_ERR_HIP, "hxv_twin_vector: staging buffers and table of the split map");
+  }
+  auto release = [&]() {
+    (void)hipStreamSynchronize(st);
+    if (e1 == hipSuccess && d_send) pool_free(to->device, d_send);
+    if (e2 == hipSuccess && d_recv) pool_free(to->device, d_recv);
+    if (d_tab) (void)hipFree(d_tab);
+  };
+  int rcx = comm_agree(to, rc_local);
+  if (rcx) {
+    release();
+    return rcx;
+  }
+  auto step_failed = [&](const char* what, hipError_t e) {
+    release();
+    return fail(HXV_ERR_HIP, std::string("hxv_twin_vector: ") + what + ": " + hipGetErrorString(e));
+  };
+  hipError_t e = hipEventRecord(to->tw_ev[0], st);
+  if (e != hipSuccess) return step_failed("event", e);
+  {
+    const unsigned gx = (unsigned)((a.dimup + TW - 1) / TW), gy = (unsigned)std::min((a.qdw + TW - 1) / TW, 65535);
+    hipLaunchKernelGGL(twin_pack_kernel, dim3(gx, gy), dim3(TW_THREADS), 0, st, (const double2*)d_psi, a.dimup, a.pitch, a.qdw, from->dev.up_iperm,
+                       from->dev.up_sign, d_send, d_recv + recv_ptr[r], (int)stride, b.dw0, b.dw0 + b.qdw);
+    e = hipGetLastError();
+    if (e != hipSuccess) return step_failed("pack kernel", e);
+  }
+  (void)hipEventRecord(to->tw_ev[1], st);
+  rcx = comm_sendrecv_cols(to, d_send, send_ptr.data(), d_recv, recv_ptr.data(), sizeof(double2), st);
+  if (rcx) {
+    release();
+    return rcx;
+  }
+  (void)hipEventRecord(to->tw_ev[2], st);
+  {
+    const unsigned gx = (unsigned)((b.pitch + TW_THREADS - 1) / TW_THREADS), gy = (unsigned)std::min(b.qdw, 65535);
+    hipLaunchKernelGGL(twin_unpack_kernel, dim3(gx, gy), dim3(TW_THREADS), 0, st, (const double2*)d_recv, (const int64_t*)d_tab, P, (double2*)d_out,
+                       b.dimup, b.pitch, b.qdw, to->dev.up_iperm, to->dev.up_sign);
+    e = hipGetLastError();
+    if (e != hipSuccess) return step_failed("unpack kernel", e);
+  }
+  (void)hipEventRecord(to->tw_ev[3], st);
+  e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return step_failed("synchronise", e);
+  for (int i = 0; i < 3; ++i) {
+    float ms = 0.f;
+    to->twin_last_us[i] = hipEventElapsedTime(&ms, to->tw_ev[i], to->tw_ev[i + 1]) == hipSuccess ? (int64_t)(ms * 1e3f + 0.5f) : -1;
+  }
+  release();
+  return HXV_OK;
+}
 }  // namespace
 
 extern "C" {
+
+int hxv_twin_split_plan(int32_t dimup_a, int32_t dimdw_a, int32_t rank, int32_t nranks, int64_t* send_counts, int64_t* recv_counts) {
+  if (!twin_split_plan(dimup_a, dimdw_a, rank, nranks, send_counts, recv_counts))
+    return fail(HXV_ERR_ARG, "hxv_twin_split_plan: bad argument (dimensions >= 1, 0 <= rank < nranks <= min(dimup_a, dimdw_a), counts not NULL)");
+  return HXV_OK;
+}
 
 int hxv_twin_vector(hxv_handle* from, hxv_handle* to, const void* d_psi, void* d_out) {
   if (!from || !to || !d_psi || !d_out) return fail(HXV_ERR_ARG, "hxv_twin_vector: NULL argument");
@@ -80,10 +267,16 @@ int hxv_twin_vector(hxv_handle* from, hxv_handle* to, const void* d_psi, void* d
     return fail(HXV_ERR_STATE, "hxv_twin_vector needs handles built from a model (basis maps)");
   if (from->device != to->device) return fail(HXV_ERR_ARG, "hxv_twin_vector: handles on different devices");
   if (d_out == d_psi) return fail(HXV_ERR_ARG, "hxv_twin_vector: d_out must not be d_psi (the map is not done in place)");
-  if (a.nranks > 1 || b.nranks > 1 || comm_ready(from) || comm_ready(to))
-    return fail(HXV_ERR_UNSUPPORTED, "hxv_twin_vector: split sectors are not supported (the twin of a DimDw split is a DimUp split: an all-to-all)");
+  const bool split = a.nranks > 1 && a.nranks == b.nranks && a.rank == b.rank;
+  if (!split && (a.nranks > 1 || b.nranks > 1 || comm_ready(from) || comm_ready(to)))
+    return fail(HXV_ERR_UNSUPPORTED, "hxv_twin_vector: split sectors are not supported unless both handles are the same rank of the same split "
+                                     "(and an unsplit pair bound to a communicator is not): the twin of a DimDw split is a DimUp split of the same ranks");
   if (a.ns != b.ns || b.nup != a.ndw || b.ndw != a.nup || b.dimup != a.dimdw || b.dimdw != a.dimup)
     return fail(HXV_ERR_ARG, "hxv_twin_vector: `to` is not the twin sector (ndw,nup) of `from`");
+  if (split) {
+    if (!comm_ready(to)) return fail(HXV_ERR_STATE, "hxv_twin_vector on a split sector needs `to` bound to a communicator (hxv_comm_init / hxv_comm_init_local)");
+    return twin_vector_split(from, to, d_psi, d_out);
+  }
   HIPCHK(hipSetDevice(to->device));
   hipStream_t st = to->stream;
   const unsigned gx = (unsigned)((a.dimup + TW - 1) / TW), gy = (unsigned)((b.pitch + TW - 1) / TW);

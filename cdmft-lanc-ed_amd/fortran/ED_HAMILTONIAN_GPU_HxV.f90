@@ -769,7 +769,9 @@ contains
   !> out = psi as a vector of its twin sector: from psi's sector (nup,ndw) into the OPEN sector, which must be (ndw,nup).  The twin branch of
   !! es_return_cvector (ED_EIGENSPACE.f90:485-494, vector(i)=twin%cvec(Order(i)), Order of ED_SETUP.f90:854-898) on the device: with ed_twin
   !! the state found in one sector of a pair serves the other one without a Dim-sized PCIe transfer.  No sign; an eigenstate of the open
-  !! sector for spin-symmetric models only (the reference warns for Nspin>1).  Split sectors are refused by the engine.
+  !! sector for spin-symmetric models only (the reference warns for Nspin>1).  On split sectors (psi's sector and the open one the same rank
+  !! of the same MpiSize, the open one bound to the communicator) psi and out are this rank's slabs and the call is collective: one
+  !! all-to-all between two kernels instead of es_return_cvector_mpi's gather on the master (ED_EIGENSPACE.f90:498-569).
   subroutine gpu_twin_vector(psi,out)
     type(gpu_vector),intent(in)    :: psi
     type(gpu_vector),intent(inout) :: out

@@ -49,7 +49,7 @@ EXPORTS = [
     "hxv_vector_alloc", "hxv_vector_alloc_many", "hxv_vector_free", "hxv_vector_from_host", "hxv_vector_to_host",
     "hxv_sector_cache_clear", "hxv_sector_cache_stats", "hxv_comm_abort", "hxv_comm_library", "hxv_comm_cache_stats", "hxv_comm_cache_clear", "hxv_host_register", "hxv_host_unregister",
     "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
-    "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_twin_vector",
+    "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_twin_vector", "hxv_twin_split_plan",
 ]
 
 _lib = None
@@ -164,6 +164,7 @@ def load_library():
     L.hxv_cluster_dm_elems.restype = i64
     L.hxv_cluster_dm_accumulate.argtypes = [vp, vp, dbl, i32, pd]
     L.hxv_twin_vector.argtypes = [vp, vp, vp, vp]
+    L.hxv_twin_split_plan.argtypes = [i32, i32, i32, i32, pi64, pi64]
     _lib = L
     return L
 
@@ -240,6 +241,15 @@ def halo_plan_from_csr(dimdw: int, rowptr, cols, rank: int, nranks: int):
     _chk(L.hxv_halo_plan_from_csr(dimdw, _p(rp, C.c_int64), _p(cl, C.c_int32), rank, nranks, _p(rc, C.c_int32), _p(sc, C.c_int32),
                                   _p(rcols, C.c_int32), _p(scols, C.c_int32), C.byref(nr), C.byref(ns)), "hxv_halo_plan_from_csr")
     return rc, sc, rcols[: nr.value], scols[: ns.value]
+
+
+def twin_split_plan(dimup_a: int, dimdw_a: int, rank: int, nranks: int):
+    """(send_counts, recv_counts) of one rank in the one exchange of the split twin-sector map (include/hxv.h, hxv_twin_split_plan): 16-byte
+    elements per rank, own entry included, for a sector A with dimup_a x dimdw_a amplitudes.  Host only: works without a GPU."""
+    sc = np.zeros(max(nranks, 1), dtype=np.int64)
+    rc = np.zeros(max(nranks, 1), dtype=np.int64)
+    _chk(load_library().hxv_twin_split_plan(dimup_a, dimdw_a, rank, nranks, _p(sc, C.c_int64), _p(rc, C.c_int64)), "hxv_twin_split_plan")
+    return sc, rc
 
 
 class LocalGroup:
@@ -854,7 +864,10 @@ class HxvSector:
         """The state psi of this sector (nup,ndw) as a vector of its twin sector `to` = (ndw,nup) (include/hxv.h, hxv_twin_vector; the twin
         branch of the reference's es_return_cvector, ED_EIGENSPACE.f90:485-494): the transpose of the amplitude matrix, without a sign, on
         the device.  psi, out: device vectors in the padded layout (localElems complex128 elements of this sector / of `to`); `out` is
-        allocated when not given, every element of it is written.  to is self is allowed where nup == ndw.  Split sectors are refused."""
+        allocated when not given, every element of it is written.  to is self is allowed where nup == ndw.
+        Split sectors: self and `to` must be the same rank of the same split, `to` joined to a communicator (self need not be); psi is this
+        rank's slab of self, the result this rank's slab of `to`, the same bits as the unsplit call's in those columns.  Collective: every
+        rank of `to`'s communicator calls it (one all-to-all between a pack and an unpack kernel)."""
         import torch
 
         assert psi.is_cuda and psi.dtype == torch.complex128 and psi.is_contiguous() and psi.numel() == self.localElems, \

@@ -386,10 +386,34 @@ int hxv_apply_ladder_axpy(hxv_handle *from, hxv_handle *to, int32_t orbital, int
  *     d_out[kB*pitch_B + rB] = sB[rB] * sA[rA] * d_psi[kA*pitch_A + rA],   kB = iperm_A[rA],  kA = iperm_B[rB]
  * (rA, rB device rows; iperm: device row -> reference row, the inverse of hxv_row_order's perm; s: the basis sign of a device row), so the
  * result is what hxv_vector_to_host / transpose / hxv_vector_from_host would give, bit for bit, whether none, one or both sectors have an order.
+ * SPLIT SECTORS: two handles that are both rank r of the same nranks > 1.  d_psi is this rank's slab of A, the columns idw in [dw0_A,
+ * dw0_A+qdw_A); d_out is this rank's slab of B, B's columns kB in [dw0_B, dw0_B+qdw_B), which are the REFERENCE up-rows of A in that range
+ * (DimDw_B = DimUp_A, both split by the one rule of ED_HAMILTONIAN.f90:93-105).  The result is the unsplit map restricted to the slab,
+ *     d_out[(kB-dw0_B)*pitch_B + perm_B[idw]] = sB[idw] * sA[kB] * d_psi[(idw-dw0_A)*pitch_A + perm_A[kB]]
+ * with each idw taken from the slab of the rank that owns it (perm, s: hxv_row_order's map and sign; the identity and +1 without a row
+ * order): bit for bit the same columns as the unsplit call.  The twin of a DimDw split is a DimUp split, so the call is COLLECTIVE over
+ * `to`'s communicator (hxv_comm_init or hxv_comm_init_local; `from` need not be bound, as in hxv_apply_ladder): every rank packs its slab
+ * by destination, ONE grouped send/receive moves the blocks, every rank unpacks (the reference gathers the whole vector on the master:
+ * es_return_cvector_mpi, ED_EIGENSPACE.f90:498-569).  Independent of the product's exchange mode.  Pad rows of d_psi are never read, d_psi
+ * is unchanged, every element of d_out is written, pad rows as zero; runs on `to`'s stream and returns when done on this rank; the two
+ * staging buffers (about one slab each) come from the device-buffer cache and go back before the call returns.  nranks > min(DimUp_A,
+ * DimDw_A) cannot arise: hxv_create_from_model refuses nranks > DimDw for either sector, and a pair opened under the communicator-shrink
+ * rule (nranks' = DimDw) has different nranks and is refused below.  hxv_get_option(to, "twin_last_pack_us" / "twin_last_exchange_us" /
+ * "twin_last_unpack_us"): what the three phases of the last split call took on the stream (HIP events; -1 before the first).
  * Errors: HXV_ERR_ARG for a NULL argument, handles on different devices, d_out == d_psi, or `to` not the sector (ndw,nup) of `from` with
- * the same Ns; HXV_ERR_STATE for handles without basis maps (from CSR, dw panels); HXV_ERR_UNSUPPORTED when either handle is split
- * (nranks > 1) or bound to a communicator: the twin of a DimDw split is a DimUp split, which needs an all-to-all -- OUT OF SCOPE here.  */
+ * the same Ns; HXV_ERR_STATE for handles without basis maps (from CSR, dw panels), and for two handles split alike whose `to` is not bound
+ * to a communicator; HXV_ERR_UNSUPPORTED when the two handles' (rank, nranks) differ (unsplit with split, 2 ranks with 3, rank 0 with
+ * rank 1) or an unsplit handle is bound to a communicator.  All of these are decided from the arguments alone, the same on every rank:
+ * they return at once, before any collective step, and write nothing.  A rank-local resource failure (staging buffers, table upload) is
+ * agreed on by all ranks before the exchange: every rank returns an error, none waits for a peer that has left.  */
 int hxv_twin_vector(hxv_handle *from, hxv_handle *to, const void *d_psi, void *d_out);
+/* The plan of the split map, not the transport: how many 16-byte elements rank `rank` of an `nranks`-way split sends to and receives from
+ * every rank (own entry included: that block stays on the device) when A has dimup_a x dimdw_a amplitudes -- no handle, no device, no
+ * communicator, in the spirit of hxv_halo_plan_from_csr; hxv_twin_vector itself sizes and addresses its buffers with these numbers.  The
+ * block p -> q holds B's columns of q (qdw_B(q), split of dimup_a) times A's columns of p (qdw_A(p), split of dimdw_a), each block row
+ * padded to a multiple of 8 elements: send_counts[q] = qdw_B(q) * roundup8(qdw_A(rank)), recv_counts[p] = qdw_B(rank) * roundup8(qdw_A(p)).
+ * HXV_ERR_ARG: a dimension < 1, rank outside [0, nranks), nranks > min(dimup_a, dimdw_a), a NULL array.  */
+int hxv_twin_split_plan(int32_t dimup_a, int32_t dimdw_a, int32_t rank, int32_t nranks, int64_t *send_counts, int64_t *recv_counts);
 
 /* ---- impurity observables of device-resident states --------------------------------------------------------------------------
  * ED_OBSERVABLES.f90 lanc_observables (:94-236), lanc_local_energy (:246-452) and the single-particle density matrix of
