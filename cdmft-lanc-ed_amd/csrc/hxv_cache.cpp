@@ -5,7 +5,8 @@
 // them (SectorImage, hxv_handle.hpp).  The key holds every byte that enters the construction and is compared byte for byte, so a new
 // bath (the next DMFT iteration) is a different key, never a stale hit.
 //   HXV_SECTOR_CACHE=0        disables it (every open builds and uploads)
-//   HXV_SECTOR_CACHE_MB=<n>   cap on the cached images' host + device bytes (default 2048), least recently used first out
+//   HXV_SECTOR_CACHE_MB=<n>   cap on the cached images' host + device bytes in whole MiB (default 2048; a fraction is dropped, so 0.5 is 0
+//                             and keeps nothing), least recently used first out
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>

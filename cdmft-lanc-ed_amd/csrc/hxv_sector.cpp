@@ -295,7 +295,7 @@ std::string row_order_env_key() {
   std::string k = row_order_enabled() ? "R1" : "R0";
   for (const char* n : {"HXV_ROW_ORDER_MIN_DIMUP", "HXV_ROW_ORDER_BITS"}) {
     const char* v = std::getenv(n);
-    k += "|";
+    k += v ? "|=" : "|";  // (set but empty is not unset: atoi reads "" as 0, the builder then takes 0 and not its default)
     if (v) k += v;
   }
   return k;

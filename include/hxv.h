@@ -489,9 +489,9 @@ int hxv_pool_stats(int32_t device, int64_t *cached_bytes, int64_t *hits, int64_t
  * N+-1).  What hxv_create_from_model builds -- basis maps, one-spin matrices, tile plan, ~50 device tables -- depends only on the model
  * bytes, (nup, ndw), (rank, nranks), the exchange and the device; the engine keeps the images of closed sectors and a re-open with the
  * same inputs shares them (identical products bit for bit; a different bath is a different key).  Environment: HXV_SECTOR_CACHE=0 disables
- * it, HXV_SECTOR_CACHE_MB caps host + device bytes (default 2048, least recently used out first).  hxv_get_option(h, "open_cache_hit" |
- * "open_us_host" | "open_us_plan" | "open_us_upload" | "open_us_total") tells what THIS open cost.  Handles from hxv_create_from_csr and
- * panel handles are not cached.                                                                                                */
+ * it, HXV_SECTOR_CACHE_MB caps host + device bytes in whole MiB (a fraction is dropped: 0.5 is 0, nothing is kept; default 2048, least
+ * recently used out first).  hxv_get_option(h, "open_cache_hit" | "open_us_host" | "open_us_plan" | "open_us_upload" | "open_us_total")
+ * tells what THIS open cost.  Handles from hxv_create_from_csr and panel handles are not cached.                                */
 int hxv_sector_cache_clear(void);
 int hxv_sector_cache_stats(int64_t *entries, int64_t *bytes, int64_t *hits, int64_t *misses); /* any out may be NULL */
 
