@@ -354,6 +354,7 @@ int hxv_destroy(hxv_handle* h) {
   pool_free(h->device, h->d_wt);
   for (auto& p : h->d_lz) pool_free(h->device, p);
   if (h->d_lz_partial) (void)hipFree(h->d_lz_partial);
+  if (h->h_probe_ov) (void)hipHostFree(h->h_probe_ov);
   for (void* v : h->owned_vectors) pool_free(h->device, v);  // (vectors the caller never freed)
   h->owned_vectors.clear();
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -871,6 +872,7 @@ int64_t hxv_get_option(const hxv_handle* h, const char* name) {
   if (!strcmp(name, "eigh_last_fused_first_steps")) return h->eigh_last_fused_first;  // restart cycles begun by tr_axpy_mdot
   if (!strcmp(name, "lanczos_real_last")) return h->last_real;
   if (!strcmp(name, "pass_b_order_last")) return h->plan.dw_order_last;  // phase order the last pass-B launch ran (0 / 1; -1: none yet)
+  if (!strcmp(name, "allreduce_count")) return h->n_allreduce;  // sum all-reduces of a split sector since creation (the drivers' dot products)
   if (!strcmp(name, "slab_copies")) return h->n_slab_copy;  // exchanges whose vector was not at home in a gather buffer
   if (!strcmp(name, "lanczos_inplace")) return h->lz_inplace;
   if (!strcmp(name, "exchange_overlap")) return h->a2a_overlap;

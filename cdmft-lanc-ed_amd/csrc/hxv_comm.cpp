@@ -409,6 +409,7 @@ int comm_lz_homes(hxv_handle* h, bool real, double2* out[3]) {
 }
 
 int comm_allreduce_sum(hxv_handle* h, double* d_buf, size_t count, hipStream_t st) {
+  if (comm_ready(h)) ++h->n_allreduce;
   if (LocalGroup* G = lg(h)) {
     // through host memory, summed in rank order on every rank: the same bits everywhere
     int rc = HXV_OK;

@@ -180,6 +180,8 @@ struct hxv_handle {
   int lz_inplace = 1;              // option "lanczos_inplace": on a split sector the Lanczos vectors live in their slot of a gather buffer (no slab copy per product)
   double* d_lz_partial = nullptr;  // per-workgroup partial sums of the fused Lanczos epilogue
   int64_t lz_partial_n = 0;
+  double* h_probe_ov = nullptr;    // page-locked host staging of hxv_lanczos_tridiag_probes: a step's overlaps land here by a truly asynchronous copy
+  int64_t probe_ov_n = 0;          // (grown on demand, freed with the handle)
   int lz_fused = 1;                // option "lanczos_fused"
   int lz_graph = 1;                // option "lanczos_graph": fixed-length tridiagonalisations run device-only, three iterations per hipGraph
   int eigh_measure_all = 0;        // option "eigh_measure_all": hxv_eigh_lowest measures every projection at every step (round-1 behaviour)
@@ -218,6 +220,7 @@ struct hxv_handle {
   double2* d_send = nullptr;     // halo exchange: packed columns, grouped by destination rank
   int32_t* d_send_cols = nullptr;
   int64_t n_exchange = 0;
+  int64_t n_allreduce = 0;       // sum all-reduces of a split sector since creation (comm_allreduce_sum with a communicator; get_option "allreduce_count")
   int64_t n_apply = 0;
   std::vector<void*> owned_vectors;      // hxv_vector_alloc'ed and not yet freed (hxv_destroy returns what is left to the buffer cache)
   int64_t h2d_bytes = 0, d2h_bytes = 0;  // vector-sized PCIe traffic of the host-array entry points and hxv_vector_from/to_host (hxv_get_stats)

@@ -164,6 +164,60 @@ __global__ void __launch_bounds__(256) lz_final(const double* __restrict__ parti
   if (threadIdx.x == 0) scal[io] = op ? sqrt(sum) : sum;
 }
 
+// PROBE OVERLAPS (hxv_lanczos_tridiag_probes): partial sums of <p_j|x> = sum conj(p_j[i]) x[i] for the M probes of one run, x and every probe
+// read once.  partial[block][2M]: (re, im) per probe.  REAL: the buffers are double[DimDw][pitch_real] viewed as double2 (see lz_len) -- two
+// consecutive real elements per load, the sum has a real part only and the imaginary slot is written as zero.  The sums are written out
+// (products rounded before they are added, one fused multiply-add per element) like lz_nrm's, so that every build adds the same numbers.
+struct LzProbes {
+  const double2* p[HXV_MAX_PROBES];
+};
+template <int M, bool REAL>
+__global__ void __launch_bounds__(256) lz_probe_dots(int64_t n, const double2* __restrict__ x, LzProbes pr, double* __restrict__ partial) {
+  double re[M], im[M];
+#pragma unroll
+  for (int j = 0; j < M; ++j) re[j] = im[j] = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const double2 a = x[i];
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      const double2 p = pr.p[j][i];
+      {
+#pragma clang fp contract(off)
+        const double t = p.x * a.x;
+        re[j] = re[j] + fma(p.y, a.y, t);
+        if (!REAL) {
+          const double u = p.x * a.y;
+          im[j] = im[j] + fma(-p.y, a.x, u);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    const double sr = block_sum(re[j]);
+    __syncthreads();  // (block_sum's buffer is read by every thread: the next sum must not overwrite it before)
+    double si = 0.0;
+    if (!REAL) {
+      si = block_sum(im[j]);
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      partial[(size_t)blockIdx.x * (2 * M) + 2 * j] = sr;
+      partial[(size_t)blockIdx.x * (2 * M) + 2 * j + 1] = si;
+    }
+  }
+}
+// out[c] = sum over the np blocks, in block order, of partial[block][c], c < nc (one workgroup)
+__global__ void __launch_bounds__(256) lz_probe_final(const double* __restrict__ partial, int np, int nc, double* __restrict__ out) {
+  for (int c = 0; c < nc; ++c) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += 256) acc += partial[(size_t)i * nc + c];
+    const double sum = block_sum(acc);
+    __syncthreads();
+    if (threadIdx.x == 0) out[c] = sum;
+  }
+}
+
 // q = w / scal[ib]
 __global__ void __launch_bounds__(256) lz_scale(int64_t n, double2* q, const double2* w,
                                                 const double* __restrict__ scal, int ib) {
@@ -648,6 +702,29 @@ struct StageFree {
   }
 };
 
+// out[2*j], out[2*j+1] = Re, Im <p_j|x> of this rank's share (n double2 elements), j < m: one pass over x and the probes, then one workgroup
+// that adds the block partials in block order.  d_part: grid_for(n) * 2m doubles.
+template <bool REAL>
+void launch_probe_dots(hxv_handle* h, int m, int64_t n, const double2* x, const LzProbes& pr, double* d_part, double* d_out) {
+  const int g = grid_for(n);
+  switch (m) {
+#define HXV_PROBE_CASE(M) \
+  case M:                 \
+    hipLaunchKernelGGL((lz_probe_dots<M, REAL>), dim3(g), dim3(256), 0, h->stream, n, x, pr, d_part); \
+    break;
+    HXV_PROBE_CASE(1)
+    HXV_PROBE_CASE(2)
+    HXV_PROBE_CASE(3)
+    HXV_PROBE_CASE(4)
+    HXV_PROBE_CASE(5)
+    HXV_PROBE_CASE(6)
+    HXV_PROBE_CASE(7)
+    HXV_PROBE_CASE(8)
+#undef HXV_PROBE_CASE
+  }
+  hipLaunchKernelGGL(lz_probe_final, dim3(1), dim3(256), 0, h->stream, d_part, g, 2 * m, d_out);
+}
+
 }  // namespace
 
 namespace hxv {
@@ -817,6 +894,185 @@ int hxv_lanczos_tridiag(hxv_handle* h, const void* d_vin, int32_t nlanc, double*
   }
   HIPCHK(hipStreamSynchronize(h->stream));
   if (nsteps) *nsteps = k;
+  return HXV_OK;
+}
+
+// hxv_lanczos_tridiag's host-stepped loop with the overlaps <p_j|q_k> of every Lanczos vector collected on the way (include/hxv.h): the
+// off-diagonal Green's functions G_ij of one orbital i from ONE run instead of the reference's mixed channels (ED_GF_NORMAL.f90:315-903).
+int hxv_lanczos_tridiag_probes(hxv_handle* h, const void* d_vin, int32_t nprobes, const void* const* d_probes, int32_t nlanc, double* alanc,
+                               double* blanc, double* overlaps, double threshold, int32_t* nsteps) {
+  if (!h) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: NULL handle");
+  HIPCHK(hipSetDevice(h->device));  // (before the first collective)
+  // scratch of the run, from the device-buffer cache and sized by nprobes: block partials of the real-vector check (start vector and probes, side
+  // by side), block partials and sums of a step's overlaps
+  double* d_ws = nullptr;
+  struct Free {
+    hxv_handle* h;
+    double*& p;
+    ~Free() {
+      if (!p) return;
+      (void)hipStreamSynchronize(h->stream);
+      pool_free(h->device, p);
+    }
+  } guard{h, d_ws};
+  const int np1 = std::max(1, std::min<int>(nprobes, HXV_MAX_PROBES));
+  const size_t n_chk = (size_t)(1 + np1) * RED_BLOCKS, n_part = (size_t)2 * np1 * RED_BLOCKS;
+  // what a rank decides from its own arguments and resources, agreed on before the first collective
+  auto check_args = [&]() -> int {
+    if (!d_vin || nlanc < 1 || !alanc || !blanc || !nsteps) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: bad argument (NULL start vector or output, or nlanc < 1)");
+    if (nprobes < 0 || nprobes > HXV_MAX_PROBES) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: nprobes must be 0 .. HXV_MAX_PROBES (8)");
+    if (nprobes > 0 && (!d_probes || !overlaps)) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: nprobes > 0 needs the probe list and the overlaps array");
+    for (int j = 0; j < nprobes; ++j) {
+      if (!d_probes[j]) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: NULL entry in the probe list");
+      // (ensure_lz clears the slab's place in the gather buffers; a START vector there is staged, a probe is the caller's to keep elsewhere)
+      if (comm_ready(h) && comm_in_gather(h, d_probes[j])) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: a probe lies in a gather buffer of the handle (hxv_slab_home): the driver clears that place");
+    }
+    HIPCHK(pool_alloc(h->device, (n_chk + n_part + 2 * np1) * sizeof(double), (void**)&d_ws));
+    // page-locked staging for the overlaps of every step: a copy into the caller's pageable array could make the runtime wait per step
+    const int64_t want = (int64_t)2 * nprobes * nlanc;
+    if (want > h->probe_ov_n) {
+      if (h->h_probe_ov) (void)hipHostFree(h->h_probe_ov);
+      h->h_probe_ov = nullptr;
+      h->probe_ov_n = 0;
+      HIPCHK(hipHostMalloc((void**)&h->h_probe_ov, (size_t)want * sizeof(double), hipHostMallocDefault));
+      h->probe_ov_n = want;
+    }
+    return HXV_OK;
+  };
+  if (int rca = comm_agree(h, check_args())) return rca;
+  if (int rcc = need_comm(h, "device Lanczos")) return rcc;
+  double *d_part = d_ws + n_chk, *d_ov = d_part + n_part;
+  const int64_t n = (int64_t)h->host.pitch * h->host.qdw;  // this rank's slab
+  const size_t real_bytes = (size_t)pitch_real_of(h) * std::max(h->host.qdw, 1) * sizeof(double);
+  StageFree staged{h, {nullptr, nullptr}};
+  double* real_probe[HXV_MAX_PROBES] = {};
+  struct FreeProbes {  // the real-mode copies of the probes go back to the buffer cache before the call returns
+    hxv_handle* h;
+    double** p;
+    ~FreeProbes() {
+      bool any = false;
+      for (int j = 0; j < HXV_MAX_PROBES; ++j) any = any || p[j];
+      if (any) (void)hipStreamSynchronize(h->stream);
+      for (int j = 0; j < HXV_MAX_PROBES; ++j)
+        if (p[j]) pool_free(h->device, p[j]);
+    }
+  } probe_guard{h, real_probe};
+  // REAL-vector mode under hxv_lanczos_tridiag's rule, AND every probe purely real: the sum of Im^2 over the start vector and the probes, over
+  // all ranks, in ONE reduction (every rank must take the same path)
+  bool real = want_real(h);
+  int rc_pre = HXV_OK;
+  if (real) {
+    const int pr = pitch_real_of(h);
+    const int g = grid_for((int64_t)pr * h->host.qdw);
+    for (int j = 0; j <= nprobes; ++j)
+      hipLaunchKernelGGL(lz_to_real, dim3(g), dim3(256), 0, h->stream, h->host.dimup, h->host.qdw, h->host.pitch, pr,
+                         (const double2*)(j ? d_probes[j - 1] : d_vin), (double*)nullptr, d_ws + (size_t)j * g);
+    rc_pre = reduce_scalar(h, d_ws, (1 + nprobes) * g, LZ_TMP, 0);
+    double im2 = 0.0;
+    if (!rc_pre && hipMemcpyAsync(&im2, h->d_scalars + LZ_TMP, sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc_pre = fail(HXV_ERR_HIP, "hxv_lanczos_tridiag_probes: reading the real-vector check failed");
+    if (!rc_pre && hipStreamSynchronize(h->stream) != hipSuccess) rc_pre = fail(HXV_ERR_HIP, "hxv_lanczos_tridiag_probes: the real-vector check failed");
+    real = im2 == 0.0;
+  }
+  auto prepare = [&]() -> int {
+    if (rc_pre) return rc_pre;
+    int r = stage_start_vector(h, d_vin, &staged.p[0]);  // (a start vector at hxv_slab_home: staged before its home is cleared)
+    if (!r) r = ensure_lz(h, real);
+    if (r) return r;
+    for (int j = 0; real && j < nprobes; ++j) HIPCHK(pool_alloc(h->device, real_bytes, (void**)&real_probe[j]));
+    return HXV_OK;
+  };
+  int rc = comm_agree(h, prepare());  // (a rank that could not allocate tells its peers before the first all-reduce)
+  if (rc) return rc;
+  LzRunner lz(h, h->lz_vec[0], h->lz_vec[1], h->lz_vec[2], real);
+  LzProbes pr{};
+  for (int j = 0; j < nprobes; ++j) {
+    if (real) launch_to_real(h, (const double2*)d_probes[j], real_probe[j], h->stream);
+    pr.p[j] = real ? (const double2*)real_probe[j] : (const double2*)d_probes[j];
+  }
+  if (real)
+    launch_to_real(h, (const double2*)d_vin, (double*)lz.b.q, h->stream);
+  else
+    HIPCHK(hipMemcpyAsync(lz.b.q, d_vin, (size_t)n * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
+  {  // the start vector's norm, as in hxv_lanczos_tridiag
+    rc = enqueue_norm(h, lz.b.q, lz.n2, LZ_TMP, 1);
+    if (rc) return rc;
+    double nrm = 0.0;
+    HIPCHK(hipMemcpyAsync(&nrm, h->d_scalars + LZ_TMP, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (!(nrm > 0.0) || !std::isfinite(nrm)) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: the start vector is zero or not finite");
+    if (std::fabs(nrm - 1.0) <= 1e-14) {
+      rc = lz.begin(1.0);
+    } else if (lz.fused) {
+      rc = lz.begin(nrm);
+    } else {
+      hipLaunchKernelGGL(lz_scale, dim3(grid_for(lz.n2)), dim3(256), 0, h->stream, lz.n2, lz.b.q, lz.b.q, h->d_scalars, LZ_TMP);
+      rc = lz.begin(1.0);
+    }
+  }
+  if (rc) return rc;
+  for (int k = 0; k < nlanc; ++k) alanc[k] = blanc[k] = 0.0;
+  for (size_t i = 0; i < (size_t)2 * nlanc * nprobes; ++i) overlaps[i] = 0.0;
+  int k = 0;
+  for (; k < nlanc; ++k) {
+    double* ov = nprobes > 0 ? overlaps + (size_t)2 * nprobes * k : nullptr;
+    double* stage = nprobes > 0 ? h->h_probe_ov + (size_t)2 * nprobes * k : nullptr;  // (a slot per step: nothing is overwritten while a copy is in flight)
+    if (nprobes > 0) {
+      // the overlaps of the STORED vector X_k, enqueued before the step that overwrites nothing of it; their copy to the host completes with
+      // the synchronisation step() makes for alpha and beta.  One all-reduce for the 2*nprobes sums of a split sector.
+      if (real)
+        launch_probe_dots<true>(h, nprobes, lz.n2, lz.vec(), pr, d_part, d_ov);
+      else
+        launch_probe_dots<false>(h, nprobes, lz.n2, lz.vec(), pr, d_part, d_ov);
+      rc = comm_allreduce_sum(h, d_ov, (size_t)2 * nprobes, h->stream);
+      if (rc) return rc;
+      HIPCHK(hipMemcpyAsync(stage, d_ov, (size_t)2 * nprobes * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    const double s = lz.scale();  // q_k = s * X_k
+    double a, bt;
+    rc = lz.step(&a, &bt);
+    if (rc) return rc;
+    for (int j = 0; j < 2 * nprobes; ++j) ov[j] = stage[j] * s;
+    alanc[k] = a;
+    if (k + 1 < nlanc) blanc[k + 1] = bt;
+    if (std::fabs(bt) < threshold) {
+      ++k;
+      break;
+    }
+    if (k + 1 < nlanc) {
+      rc = lz.advance();
+      if (rc) return rc;
+    }
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  *nsteps = k;
+  return HXV_OK;
+}
+
+// Poles and weights of <p_j|(z - H)^{-1}|v> from one run of hxv_lanczos_tridiag_probes (include/hxv.h).  Host code only.
+int hxv_gf_from_probes(int32_t nsteps, const double* alanc, const double* blanc, int32_t nprobes, const double* overlaps, double norm,
+                       double* poles, double* weights) {
+  if (nsteps < 1 || !alanc || !blanc || !poles || nprobes < 0 || (nprobes > 0 && (!overlaps || !weights)))
+    return fail(HXV_ERR_ARG, "hxv_gf_from_probes: bad argument (nsteps < 1, nprobes < 0 or a NULL array)");
+  const int m = nsteps;
+  std::vector<double> d(alanc, alanc + m), e(blanc, blanc + m), z((size_t)m * m, 0.0);
+  for (int i = 0; i < m; ++i) z[i + (size_t)i * m] = 1.0;
+  if (!tridiag_ql(m, d, e, &z)) return fail(HXV_ERR_STATE, "hxv_gf_from_probes: tridiagonal QL did not converge");
+  std::vector<int> order(m);
+  for (int i = 0; i < m; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return d[a] < d[b] || (d[a] == d[b] && a < b); });  // poles ascending
+  for (int o = 0; o < m; ++o) {
+    const double* zn = &z[(size_t)order[o] * m];  // eigenvector of pole o: T = Z diag(poles) Z^T
+    poles[o] = d[order[o]];
+    for (int j = 0; j < nprobes; ++j) {
+      double re = 0.0, im = 0.0;  // sum_k o_kj Z_kn
+      for (int k = 0; k < m; ++k) {
+        re += overlaps[2 * ((size_t)k * nprobes + j)] * zn[k];
+        im += overlaps[2 * ((size_t)k * nprobes + j) + 1] * zn[k];
+      }
+      weights[2 * ((size_t)o * nprobes + j)] = norm * zn[0] * re;
+      weights[2 * ((size_t)o * nprobes + j) + 1] = norm * zn[0] * im;
+    }
+  }
   return HXV_OK;
 }
 

@@ -39,6 +39,9 @@ module ED_HAMILTONIAN_GPU_HXV
   public :: gpu_twin_vector
   public :: gpu_sp_lanc_tridiag_dev
   public :: gpu_sp_lanc_tridiag_pair_dev
+  !off-diagonal Green's functions from one run per orbital (include/hxv.h: hxv_lanczos_tridiag_probes, hxv_gf_from_probes)
+  public :: gpu_sp_lanc_tridiag_probes_dev
+  public :: gpu_gf_from_probes
   public :: gpu_vector_to_host
   public :: gpu_vector_from_host
   public :: gpu_free_vector
@@ -290,6 +293,24 @@ module ED_HAMILTONIAN_GPU_HXV
        real(c_double),value     :: threshold
        integer(c_int32_t)       :: nsteps_a,nsteps_b
      end function hxv_lanczos_tridiag_pair
+     integer(c_int) function hxv_lanczos_tridiag_probes(h,d_vin,nprobes,d_probes,nlanc,alanc,blanc,overlaps,threshold,nsteps) &
+          bind(C,name="hxv_lanczos_tridiag_probes")
+       import :: c_int, c_int32_t, c_ptr, c_double, c_double_complex
+       type(c_ptr),value         :: h,d_vin
+       integer(c_int32_t),value  :: nprobes,nlanc
+       type(c_ptr)               :: d_probes(*)
+       real(c_double)            :: alanc(*),blanc(*)
+       complex(c_double_complex) :: overlaps(*)
+       real(c_double),value      :: threshold
+       integer(c_int32_t)        :: nsteps
+     end function hxv_lanczos_tridiag_probes
+     integer(c_int) function hxv_gf_from_probes(nsteps,alanc,blanc,nprobes,overlaps,norm,poles,weights) bind(C,name="hxv_gf_from_probes")
+       import :: c_int, c_int32_t, c_double, c_double_complex
+       integer(c_int32_t),value  :: nsteps,nprobes
+       real(c_double)            :: alanc(*),blanc(*),poles(*)
+       complex(c_double_complex) :: overlaps(*),weights(*)
+       real(c_double),value      :: norm
+     end function hxv_gf_from_probes
      integer(c_int) function hxv_apply_ladder_axpy(from,to,orbital,spin,create,coef_re,coef_im,accumulate,d_psi,d_out,norm2) &
           bind(C,name="hxv_apply_ladder_axpy")
        import :: c_int, c_int32_t, c_ptr, c_double
@@ -814,6 +835,64 @@ contains
     call check(hxv_lanczos_tridiag_pair(handle,vin_a%d,vin_b%d,int(size(alanc_a),c_int32_t),alanc_a,blanc_a,alanc_b,blanc_b,thr,na,nb),&
          "gpu_sp_lanc_tridiag_pair_dev")
   end subroutine gpu_sp_lanc_tridiag_pair_dev
+
+  !> gpu_sp_lanc_tridiag_dev with PROBE vectors (include/hxv.h, hxv_lanczos_tridiag_probes): besides alanc / blanc the overlaps
+  !! overlaps(j,k) = <probes(j)|q_k> of every unit Lanczos vector q_k, k = 1..nsteps, with up to 8 device vectors of the open sector (e.g.
+  !! c^dagger_j|gs> for the other orbitals j while the run starts from c^dagger_i|gs>): what gpu_gf_from_probes turns into the off-diagonal
+  !! Green's functions of orbital i, so that ONE run per orbital replaces lanc_build_gf_normal_mix_chan2/4 (ED_GF_NORMAL.f90:315-903).
+  !! overlaps is (size(probes), size(alanc)); columns of steps that did not run are zero; nsteps = the steps done.
+  subroutine gpu_sp_lanc_tridiag_probes_dev(vin,probes,alanc,blanc,overlaps,threshold,nsteps)
+    type(gpu_vector),intent(in)  :: vin
+    type(gpu_vector),intent(in)  :: probes(:)
+    real(8),intent(inout)        :: alanc(:),blanc(:)
+    complex(8),intent(inout)     :: overlaps(:,:)
+    real(8),intent(in),optional  :: threshold
+    integer,intent(out),optional :: nsteps
+    real(8)                      :: thr
+    integer(c_int32_t)           :: ns
+    type(c_ptr)                  :: plist(8)
+    complex(8),allocatable       :: ov(:,:)
+    integer                      :: j
+    if(.not.c_associated(handle))stop "gpu_sp_lanc_tridiag_probes_dev ERROR: Hsector NOT set"
+    if(vin%sector_id/=handle_serial.or..not.c_associated(vin%d))stop "gpu_sp_lanc_tridiag_probes_dev ERROR: the start vector does not belong to the open sector"
+    if(size(probes)>8)stop "gpu_sp_lanc_tridiag_probes_dev ERROR: more than 8 probes"
+    if(size(overlaps,1)/=size(probes).or.size(overlaps,2)/=size(alanc).or.size(blanc)/=size(alanc))&
+         stop "gpu_sp_lanc_tridiag_probes_dev ERROR: overlaps must be (size(probes),size(alanc)), blanc as long as alanc"
+    plist=c_null_ptr
+    do j=1,size(probes)
+       if(probes(j)%sector_id/=handle_serial.or..not.c_associated(probes(j)%d))stop "gpu_sp_lanc_tridiag_probes_dev ERROR: a probe does not belong to the open sector"
+       plist(j)=probes(j)%d
+    enddo
+    thr=1d-12; if(present(threshold))thr=threshold
+    allocate(ov(max(size(probes),1),size(alanc)))      !(contiguous, whatever section the caller passed)
+    call check(hxv_lanczos_tridiag_probes(handle,vin%d,int(size(probes),c_int32_t),plist,int(size(alanc),c_int32_t),alanc,blanc,ov,thr,ns),&
+         "gpu_sp_lanc_tridiag_probes_dev")
+    if(size(probes)>0)overlaps=ov
+    if(present(nsteps))nsteps=int(ns)
+  end subroutine gpu_sp_lanc_tridiag_probes_dev
+
+  !> Poles and weights from one probes run (include/hxv.h, hxv_gf_from_probes; host code only, the engine's own tridiagonal QL): with
+  !! alanc, blanc and overlaps(:,1:nsteps) of gpu_sp_lanc_tridiag_probes_dev and norm = |v| of the unnormalised start vector (sqrt of
+  !! gpu_apply_ladder's norm2),   <probes(j)|(z - H)^-1|v> ~ sum_n weights(j,n) / (z - poles(n)),   n = 1..size(alanc).
+  !! In the reference's conventions (add_to_lanczos_gf_normal, ED_GF_NORMAL.f90:915-975): de = poles(n) - Ei, a c^dagger channel (isign = +1)
+  !! adds weights(j,n)/(z - de), a c channel (isign = -1) adds weights(j,n)/(z + de).
+  subroutine gpu_gf_from_probes(alanc,blanc,overlaps,norm,poles,weights)
+    real(8),intent(in)       :: alanc(:),blanc(:)
+    complex(8),intent(in)    :: overlaps(:,:)
+    real(8),intent(in)       :: norm
+    real(8),intent(inout)    :: poles(:)
+    complex(8),intent(inout) :: weights(:,:)
+    real(8),allocatable      :: a(:),b(:)
+    complex(8),allocatable   :: ov(:,:),w(:,:)
+    integer                  :: n,np
+    n=size(alanc); np=size(overlaps,1)
+    if(size(blanc)/=n.or.size(overlaps,2)/=n.or.size(poles)/=n.or.size(weights,1)/=np.or.size(weights,2)/=n)&
+         stop "gpu_gf_from_probes ERROR: alanc, blanc, poles of one length n; overlaps, weights (nprobes,n)"
+    allocate(a(n),b(n),ov(max(np,1),n),w(max(np,1),n))  !(contiguous copies, whatever sections the caller passed)
+    a=alanc; b=blanc; ov=(0d0,0d0); if(np>0)ov=overlaps
+    call check(hxv_gf_from_probes(int(n,c_int32_t),a,b,int(np,c_int32_t),ov,norm,poles,w),"gpu_gf_from_probes")
+    if(np>0)weights=w
+  end subroutine gpu_gf_from_probes
 
   !> the vector in the reference's host layout (this rank's slab), when it is wanted there after all (e.g. state_list of ED_DIAG)
   subroutine gpu_vector_to_host(vect,v)

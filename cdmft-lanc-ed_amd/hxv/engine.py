@@ -50,6 +50,7 @@ EXPORTS = [
     "hxv_sector_cache_clear", "hxv_sector_cache_stats", "hxv_comm_abort", "hxv_comm_library", "hxv_comm_cache_stats", "hxv_comm_cache_clear", "hxv_host_register", "hxv_host_unregister",
     "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
     "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_twin_vector", "hxv_twin_split_plan",
+    "hxv_lanczos_tridiag_probes", "hxv_gf_from_probes",
 ]
 
 _lib = None
@@ -165,6 +166,8 @@ def load_library():
     L.hxv_cluster_dm_accumulate.argtypes = [vp, vp, dbl, i32, pd]
     L.hxv_twin_vector.argtypes = [vp, vp, vp, vp]
     L.hxv_twin_split_plan.argtypes = [i32, i32, i32, i32, pi64, pi64]
+    L.hxv_lanczos_tridiag_probes.argtypes = [vp, vp, i32, C.POINTER(vp), i32, pd, pd, pd, dbl, pi32]
+    L.hxv_gf_from_probes.argtypes = [i32, pd, pd, i32, pd, dbl, pd, pd]
     _lib = L
     return L
 
@@ -743,6 +746,31 @@ class HxvSector:
         _chk(load_library().hxv_lanczos_tridiag(self._h, vin.data_ptr(), nlanc, _p(a, C.c_double), _p(b, C.c_double), threshold,
                                                 C.byref(n)), "hxv_lanczos_tridiag")
         return a, b, n.value
+
+    def lanczos_tridiag_probes(self, vin, probes, nlanc: int, threshold: float = 1e-12):
+        """hxv_lanczos_tridiag_probes (include/hxv.h): the tridiagonalisation from `vin` together with the overlaps <p_j|q_k> of every unit
+        Lanczos vector q_k with the probe vectors -- what hxv.greens.poles_weights turns into <p_j|(z - H)^-1|vin>, the off-diagonal Green's
+        functions of one orbital from ONE run.  vin and every probe are device vectors of this sector in the padded layout (localElems
+        complex128 elements, as apply_ladder / twin_vector / lanczos_eigh(native=True) return them; this rank's slab on a split sector,
+        collective there); at most 8 probes, none is allowed.  -> (alanc, blanc, overlaps[nsteps, nprobes] complex128, nsteps)."""
+        import torch
+
+        probes = list(probes)
+        for v in [vin] + probes:
+            if not (torch.is_tensor(v) and v.is_cuda and v.dtype == torch.complex128 and v.is_contiguous() and v.numel() == self.localElems):
+                raise HxvError("lanczos_tridiag_probes takes device vectors in the padded layout (complex128, localElems = "
+                               f"{self.localElems} elements); use pad() / vector_from_host() for a vector in the reference's layout")
+        torch.cuda.synchronize()
+        npr = len(probes)
+        a = np.zeros(nlanc)
+        b = np.zeros(nlanc)
+        ov = np.zeros((max(nlanc, 0), npr), dtype=np.complex128)
+        n = C.c_int32()
+        plist = (C.c_void_p * max(npr, 1))(*[p.data_ptr() for p in probes])
+        _chk(load_library().hxv_lanczos_tridiag_probes(self._h, vin.data_ptr(), npr, plist if npr else None, nlanc, _p(a, C.c_double), _p(b, C.c_double),
+                                                       C.cast(ov.ctypes.data, C.POINTER(C.c_double)) if npr else None, threshold, C.byref(n)),
+             "hxv_lanczos_tridiag_probes")
+        return a, b, ov[: n.value], n.value
 
     def lanczos_tridiag_pair(self, vin_a, vin_b, nlanc: int, threshold: float = 1e-12):
         """Two sp_lanc_tridiag runs (two Green's-function channels) on one product, real H: vin_a, vin_b = REAL start vectors in

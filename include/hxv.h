@@ -316,6 +316,57 @@ int hxv_lanczos_tridiag_pair(hxv_handle *h, const void *d_vin_a, const void *d_v
 int hxv_lanczos_tridiag_pair_host(hxv_handle *h, const void *vin_a_host, const void *vin_b_host, int32_t nlanc, double *alanc_a,
                                   double *blanc_a, double *alanc_b, double *blanc_b, double threshold, int32_t *nsteps_a,
                                   int32_t *nsteps_b);
+/* ---- OFF-DIAGONAL Green's functions from one run per orbital.  The reference recovers G_ij from three diagonal-type continued fractions,
+ * G_ij = 1/2 (G_{i+j} - G_ii - G_jj), and runs a tridiagonalisation per mixed start vector for it (lanc_build_gf_normal_mix_chan2/4,
+ * ED_GF_NORMAL.f90:315-903: 48 of the 56 runs of a 2x2 solve).  The Krylov space of v = c^dagger_i|gs> already holds the Galerkin solution of
+ * (z - H) x = v,  x_m(z) = |v| sum_k q_k [(z - T)^{-1}]_{k1},  so <p|(z - H)^{-1}|v> for any other vector p needs only the overlaps
+ * o_k = <p|q_k> of the Lanczos vectors with p, collected while the run for G_ii is under way: one extra streaming pass per step over the
+ * Lanczos vector and the probes.  H Q = Q T + beta q_{m+1} e_m^T holds locally to rounding whether or not the q_k stay orthogonal, so the
+ * result does not rely on re-orthogonalisation.
+ * hxv_lanczos_tridiag_probes: hxv_lanczos_tridiag with up to HXV_MAX_PROBES probe vectors.
+ *   alanc, blanc, *nsteps : what hxv_lanczos_tridiag returns for the same d_vin on the same handle, bit for bit, whenever both take the same
+ *     vector path (below): the same recurrence, run through the host-stepped loop (the graph-captured path is bit-identical to it; a split
+ *     sector runs the host loop anyway).  The start vector is normalised by the driver when it is not.
+ *   overlaps[2*(k*nprobes + j)], [.. + 1] = Re, Im <p_j|q_k> = sum conj(p_j[i]) q_k[i] for k < *nsteps, q_k the UNIT Lanczos vector of step k
+ *     (q_0 = d_vin / |d_vin|); entries of steps that did not run are zero.  The probes are used as given: their norm is the caller's business.
+ *     A probe may be d_vin itself: its first overlap is the start vector's norm, the later ones measure the loss of orthogonality.
+ *   d_probes : nprobes device vectors of the sector (this rank's slab, hxv_localvec_elems() elements, pad rows zero, like d_vin); nprobes = 0
+ *     (d_probes, overlaps may be NULL) is a plain stepwise tridiagonalisation.
+ * The overlaps of q_k are computed before the product of step k, in one pass that reads q_k and every probe once (no floating-point atomics:
+ * the same vectors give the same bits on every call), and reach the host -- a page-locked staging array of the handle -- with the
+ * synchronisation the step makes for alpha and beta.
+ * REAL-vector mode: the run is real when hxv_lanczos_tridiag's rule holds (option "real_vectors", H real, Im(d_vin) == 0 on all ranks) AND
+ * every probe has zero imaginary part on all ranks -- one reduction for all of them; the probes are then converted once into buffers from the
+ * device-buffer cache, which go back before the call returns, and the imaginary parts of the overlaps are exactly zero.  Otherwise the
+ * complex path runs (a complex probe of a real start vector: alanc / blanc then equal hxv_lanczos_tridiag's with option "real_vectors" = 0).
+ * "lanczos_real_last" reports the path.  No basis maps are needed: handles from hxv_create_from_csr, with the spH0nd block, and with option
+ * "lanczos_fused" = 0 work alike.
+ * SPLIT SECTORS: the rules of hxv_lanczos_tridiag; the 2*nprobes partial sums of a step are summed over the ranks in ONE all-reduce (get
+ * "allreduce_count" counts a handle's sum all-reduces); argument and allocation failures are agreed on by all ranks before the first collective
+ * step.  A start vector at hxv_slab_home is staged as in hxv_lanczos_tridiag; a PROBE inside one of the handle's gather buffers is refused
+ * on every rank together, with nobody left in a collective (HXV_ERR_ARG on the rank whose probe it is; its peers get the error the agreement
+ * hands them, HXV_ERR_ARG or HXV_ERR_STATE depending on the transport): the driver clears that place.
+ * Errors: HXV_ERR_ARG for a NULL handle, d_vin, alanc, blanc or nsteps, nlanc < 1, nprobes outside [0, HXV_MAX_PROBES], nprobes > 0 with a
+ * NULL list, a NULL entry or NULL overlaps, a zero or non-finite start vector.
+ * Not provided: two probe runs paired as Re / Im of one complex vector, a graph-captured form, a host-vector form.                      */
+#define HXV_MAX_PROBES 8
+int hxv_lanczos_tridiag_probes(hxv_handle *h, const void *d_vin, int32_t nprobes, const void *const *d_probes, int32_t nlanc, double *alanc,
+                               double *blanc, double *overlaps /* [nlanc][nprobes] complex, interleaved, step-major */, double threshold,
+                               int32_t *nsteps);
+/* From the overlaps to poles and weights (pure host code, no device):  T = Z diag(lambda) Z^T  of the nsteps x nsteps tridiagonal matrix
+ * (alanc, blanc as returned above; the engine's own implicit QL, no LAPACK),
+ *     poles[n] = lambda_n (ascending),   weights[2*(n*nprobes + j)], [.. + 1] = Re, Im of  norm * Z_{1n} * sum_k o_kj Z_kn,
+ * so that  <p_j|(z - H)^{-1}|v>  ~  sum_n weights[n][j] / (z - poles[n]),  norm = |v| of the UNNORMALISED start vector (the square root of
+ * hxv_apply_ladder's *norm2).  For p = v (the unnormalised d_vin given as a probe of its own run) the weight is norm^2 Z_{1n}^2, the reference's own formula
+ * (ED_GF_NORMAL.f90:949-973).  In the reference's conventions (add_to_lanczos_gf_normal, :915-975) the channel c^dagger (isign = +1) adds
+ * weights / (z - (poles - E0)) and the channel c (isign = -1) adds weights / (z + (poles - E0)) to impGmatrix, E0 the ground-state energy.
+ * With v = c^dagger_i|gs> and p_j = c^dagger_j|gs> the sum is the particle part of G_ji; with v = c_i|gs>, p_j = c_j|gs> and the pole sign
+ * flipped it is the hole part of G_ij.
+ * Errors: HXV_ERR_ARG for nsteps < 1, nprobes < 0 or a NULL array (overlaps / weights may be NULL when nprobes == 0); HXV_ERR_STATE when the
+ * QL iteration does not converge.                                                                                                      */
+int hxv_gf_from_probes(int32_t nsteps, const double *alanc, const double *blanc, int32_t nprobes, const double *overlaps,
+                       double norm /* |v| of the unnormalised start vector */, double *poles /* [nsteps] */,
+                       double *weights /* [nsteps][nprobes] complex */);
 /* ---- Several lowest eigenpairs on device: the call SciFortran's sp_eigh (P-ARPACK) serves at ED_DIAG.f90:152-160,
  *   call sp_eigh(spHtimesV_p, eig_values(Neigen), eig_basis(vecDim,Neigen), Nblock, Nitermax, tol=lanc_tolerance)
  * as a thick-restart Lanczos (the explicit-restart form of ARPACK's implicitly restarted Lanczos for Hermitian
@@ -558,7 +609,7 @@ int hxv_get_diag(const hxv_handle *h, double *diag);
  * driver read-backs ("pass_b_order_last": the phase order the last pass-B launch ran, 1 = out-of-block sums in registers, 0 = the earlier
  * order [eight pairs per thread, row-major scratch patches, a largest block that leaves no room for wt_cols - 1 dead columns, debug bit 8192],
  * -1 = no launch since the plan was made; "lanczos_real_last", "eigh_last_full_passes", "eigh_last_local_passes", "eigh_last_search_products",
- * "eigh_last_check_products", "slab_copies"; which restart code the last hxv_eigh_lowest ran: "eigh_last_restarts" thick restarts of the search
+ * "eigh_last_check_products", "slab_copies", "allreduce_count" (the sum all-reduces a split sector's drivers have made on this handle); which restart code the last hxv_eigh_lowest ran: "eigh_last_restarts" thick restarts of the search
  * round, "eigh_last_fused_restarts" those whose rotation also measured the residual vector, "eigh_last_fused_first_steps" restart cycles whose
  * first step removed the arrow and measured in one pass) and what the open cost ("open_cache_hit", "open_us_host|plan|upload|total").
  * Every option of groups 1 and 2 reads back the value hxv_set_option stored ("tile_bits_up|_dw": the block bits of the plan in use;
