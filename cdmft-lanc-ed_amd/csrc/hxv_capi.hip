@@ -925,6 +925,8 @@ int64_t hxv_get_option(const hxv_handle* h, const char* name) {
   if (!strcmp(name, "bh_dw_x100")) return (int64_t)(100 * h->plan.dw.bh_per_row);
   if (!strcmp(name, "rs_dw_x100")) return (int64_t)(100 * h->plan.dw.rs_per_row);
   if (!strcmp(name, "max_block_up")) return h->plan.up.max_block;
+  if (!strcmp(name, "ncoef_up")) return h->plan.ncoef_up;  // distinct hopping amplitudes: the kernels' coefficient tables hold 2 * ncoef + 1 words
+  if (!strcmp(name, "ncoef_dw")) return h->plan.ncoef_dw;
   if (!strcmp(name, "max_block_dw")) return h->plan.dw.max_block;
   if (!strcmp(name, "nblocks_up")) return h->plan.up.nblocks;
   if (!strcmp(name, "table_classes_up")) return h->plan.up.table_classes;

@@ -18,6 +18,12 @@
 #ifndef HXV_PAIR_LDS
 #define HXV_PAIR_LDS 1  // (0: A/B builds only -- the real-vector pass A with one 8-byte LDS element per column)
 #endif
+// How a workgroup of pass A starts (LABNOTES "How a workgroup starts").  -DHXV_SERIAL_TILE_LOAD=1 builds the earlier order -- one load /
+// wait / store loop per tile column, the block's words read behind the barrier -- for A/B runs (scripts/build_variant.py); the results
+// are bit-identical.
+#ifndef HXV_SERIAL_TILE_LOAD
+#define HXV_SERIAL_TILE_LOAD 0
+#endif
 
 namespace hxv {
 
@@ -80,26 +86,29 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_up(DevSector s, DevTiles t, 
   // complex kernel, for which the hop lists were dealt over the banks.  Same FMAs in the same order: bit-identical results.
   constexpr bool PL = HXV_PAIR_LDS && sizeof(VT) == 8 && (C % 2 == 0);
   auto lidx = [&](int cc, int r) -> int { return PL ? ((((cc >> 1) * n + r) << 1) + (cc & 1)) : cc * n + r; };
-  if constexpr (PL) {
-    double2* l2 = reinterpret_cast<double2*>(lds);
+  if constexpr (HXV_SERIAL_TILE_LOAD) {
+    // (A/B builds only) the load phase as it was: one loop per column, each waiting for its line before the next column's is asked for
+    if constexpr (PL) {
+      double2* l2 = reinterpret_cast<double2*>(lds);
 #pragma unroll
-    for (int pc = 0; pc < C / 2; ++pc) {
-      const VT* __restrict__ sa = vcol0 + (int64_t)min(2 * pc, nc - 1) * s.pitch + r0;
-      const VT* __restrict__ sb = vcol0 + (int64_t)min(2 * pc + 1, nc - 1) * s.pitch + r0;
-      for (int r = threadIdx.x; r < n; r += T) l2[pc * n + r] = make_double2((double)sa[r], (double)sb[r]);
-    }
-  } else {
+      for (int pc = 0; pc < C / 2; ++pc) {
+        const VT* __restrict__ sa = vcol0 + (int64_t)min(2 * pc, nc - 1) * s.pitch + r0;
+        const VT* __restrict__ sb = vcol0 + (int64_t)min(2 * pc + 1, nc - 1) * s.pitch + r0;
+        for (int r = threadIdx.x; r < n; r += T) l2[pc * n + r] = make_double2((double)sa[r], (double)sb[r]);
+      }
+    } else {
 #pragma unroll
-    for (int cc = 0; cc < C; ++cc) {
-      const VT* __restrict__ src = vcol0 + (int64_t)min(cc, nc - 1) * s.pitch + r0;
-      for (int r = threadIdx.x; r < n; r += T) lds[cc * n + r] = src[r];
+      for (int cc = 0; cc < C; ++cc) {
+        const VT* __restrict__ src = vcol0 + (int64_t)min(cc, nc - 1) * s.pitch + r0;
+        for (int r = threadIdx.x; r < n; r += T) lds[cc * n + r] = src[r];
+      }
     }
+    for (int q = threadIdx.x; q < t.nscoef; q += T) lcoef[q] = Coef<REAL>::from(t.scoef[q]);
   }
-  for (int q = threadIdx.x; q < t.nscoef; q += T) lcoef[q] = Coef<REAL>::from(t.scoef[q]);
   uint32_t* lrq = reinterpret_cast<uint32_t*>(lcoef + t.nscoef);  // (ND only; the launcher adds the bytes)
   const int nvp = ND ? s.nd.nlat * s.nd.norb * (s.nd.norb - 1) : 0;  // ordered pairs of different orbitals of a site
   uint32_t* lnd = lrq + nvp;
-  if constexpr (ND) {
+  auto nd_tables = [&]() {
     const int O = s.nd.norb;
     for (int idx = threadIdx.x; idx < nvp * 2 * C; idx += T) {
       const int pp = idx / (2 * C), kind = (idx / C) & 1, cc = idx % C;
@@ -115,7 +124,8 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_up(DevSector s, DevTiles t, 
       lnd[idx] = w;
       if (kind == 0 && cc == 0) lrq[pp] = (uint32_t)rq;
     }
-  }
+  };
+  if constexpr (ND && HXV_SERIAL_TILE_LOAD) nd_tables();
   const uint32_t p16m = (1u << t.p16_bits) - 1u;  // half-size table words: (coefficient index << p16_bits) | offset
   double asum = 0.0;
   // one row per thread (the plan guarantees n <= blockDim.x)
@@ -168,11 +178,55 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_up(DevSector s, DevTiles t, 
       }
     }
   };
+  // What depends only on the block and the wave is asked for in front of the barrier, so that it arrives behind the tile load instead of
+  // behind the barrier: the wave's in-block list length (with the tile loads; one register carries it over the barrier) and the ranges of
+  // the block hops and the row slots.
+  constexpr bool EARLY_KB = !HXV_SERIAL_TILE_LOAD;
+  uint32_t gm_early = 0, bh_lo = 0, bh_hi = 0, rs_lo = 0, rs_hi = 0;
+  const uint32_t* __restrict__ gm_src = t.gmax + t.gstart[kb];
+  if constexpr (EARLY_KB) {
+    bh_lo = t.bh_ptr[kb];
+    bh_hi = t.bh_ptr[kb + 1];
+    rs_lo = t.rs_ptr[kb];
+    rs_hi = t.rs_ptr[kb + 1];
+  }
+  if constexpr (!HXV_SERIAL_TILE_LOAD) {
+    // The load phase is straight-line code: a thread with a row asks for its C tile elements, the wave's list length and a coefficient word
+    // back to back -- one round trip to memory with all of them in flight -- and stores to LDS as the answers arrive.  (As one loop per
+    // column -- the compiler cannot know that n <= blockDim.x makes each run once -- every column's line was waited for before the next was
+    // asked for: four dependent round trips and a fifth for the coefficients.)  No branch lies between the loads and the stores -- the
+    // compiler moves a load down to the block of its first use -- so the coefficient word has no guard: threads past the table copy its
+    // last word once more.  The accumulators' loads follow the stores and stay in flight across the barrier: ahead of the stores, they
+    // and the tile do not fit the 64 registers -- the scheduler then moves half of the tile loads below the first store
+    // (LABNOTES, "How a workgroup starts").
+    if (p < n) {
+      const int qc = min(p, t.nscoef - 1);
+      VT tx[C];
+      const VT* __restrict__ src = vcol0 + r0 + p;
+#pragma unroll
+      for (int cc = 0; cc < C; ++cc) tx[cc] = src[(int64_t)min(cc, nc - 1) * s.pitch];
+      gm_early = gm_src[p >> 6];
+      const double2 cw = t.scoef[qc];
+      if constexpr (PL) {
+        double2* l2 = reinterpret_cast<double2*>(lds);
+#pragma unroll
+        for (int pc = 0; pc < C / 2; ++pc) l2[pc * n + p] = make_double2((double)tx[2 * pc], (double)tx[2 * pc + 1]);
+      } else {
+#pragma unroll
+        for (int cc = 0; cc < C; ++cc) lds[cc * n + p] = tx[cc];
+      }
+      lcoef[qc] = Coef<REAL>::from(cw);
+    } else if (p < t.nscoef) {  // (a block with fewer rows than there are coefficients)
+      lcoef[p] = Coef<REAL>::from(t.scoef[p]);
+    }
+    for (int q = p + T; q < t.nscoef; q += T) lcoef[q] = Coef<REAL>::from(t.scoef[q]);  // (a table longer than the workgroup: up to 511 words on 256 threads)
+    if constexpr (ND) nd_tables();
+  }
   row_inputs();
   __syncthreads();
   VT xq[LZ ? C : 1];  // the thread's own input elements, kept for the Lanczos epilogue
   if (p < n) {
-    const uint32_t packed = __builtin_amdgcn_readfirstlane(t.gmax[t.gstart[kb] + (p >> 6)]);
+    const uint32_t packed = __builtin_amdgcn_readfirstlane(EARLY_KB ? gm_early : gm_src[p >> 6]);
     const int kin = (int)(packed & 0xFFFFu);
     if (LZ) {
 #pragma unroll
@@ -196,19 +250,21 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_up(DevSector s, DevTiles t, 
     // hops that leave the block, same columns, other rows: from global memory (L2 of this XCD)
     if (!(t.debug & 1)) {
       // block hops: the partner block is one contiguous run, lanes read consecutive rows
-      for (uint32_t h = t.bh_ptr[kb]; h < ((t.debug & 256) ? t.bh_ptr[kb] : t.bh_ptr[kb + 1]); ++h) {
+      const uint32_t bh0 = EARLY_KB ? bh_lo : t.bh_ptr[kb], bh1 = EARLY_KB ? bh_hi : t.bh_ptr[kb + 1];
+      for (uint32_t h = bh0; h < ((t.debug & 256) ? bh0 : bh1); ++h) {
         const CT cf = lcoef[t.bh[2 * h + 1]];
         const VT* __restrict__ src = vcol0 + t.bh[2 * h] + r;
 #pragma unroll
         for (int cc = 0; cc < C; ++cc) Coef<REAL>::fma(acc[cc], cf, src[(int64_t)min(cc, nc - 1) * s.pitch]);
       }
       // row slots: one table word per row and (block, source block) pair -- or, packed, per TWO such pairs (P16)
-      const uint32_t rs1 = (t.debug & 512) ? t.rs_ptr[kb] : t.rs_ptr[kb + 1];
+      const uint32_t rs0 = EARLY_KB ? rs_lo : t.rs_ptr[kb];
+      const uint32_t rs1 = (t.debug & 512) ? rs0 : (EARLY_KB ? rs_hi : t.rs_ptr[kb + 1]);
       // (eight-column tiles -- real vectors -- keep one word per slot: with the packed words the fused real-vector pass A went from
       //  1.67 to 1.88 ms at C3, the whole round-3 regression of the real Lanczos iteration, 3.77 -> 3.96 ms; profiles/r04_bisect_real.log)
       if (P16 && C < 8 && t.rs16) {
         const uint32_t empty16 = (uint32_t)(t.nscoef - 1) << t.p16_bits;
-        for (uint32_t sl = t.rs_ptr[kb]; sl < rs1; sl += 2) {
+        for (uint32_t sl = rs0; sl < rs1; sl += 2) {
           const uint32_t w = t.rs16[t.rs16_off[sl] + r];
 #pragma unroll
           for (int hh = 0; hh < 2; ++hh) {
@@ -225,7 +281,7 @@ __global__ void __launch_bounds__(1024, 8) hxv_pass_up(DevSector s, DevTiles t, 
         }
       } else {
         const uint32_t emptyz = (uint32_t)(t.nscoef - 1) << TILE_COEF_SHIFT;
-        for (uint32_t sl = t.rs_ptr[kb]; sl < rs1; ++sl) {
+        for (uint32_t sl = rs0; sl < rs1; ++sl) {
           const uint32_t e = t.rs_tab[t.rs_off[sl] + r];
           if (__all(e == emptyz)) continue;
           CT cf = lcoef[e >> TILE_COEF_SHIFT];

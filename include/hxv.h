@@ -605,7 +605,7 @@ int hxv_get_diag(const hxv_handle *h, double *diag);
  *   (out-of-block hops after the in-block ones, their sums added into the LDS tile) also where the plan allows the out-of-block sums in
  *   registers.
  *
- * hxv_get_option additionally reports plan statistics ("tile_bits_up", "nblocks_up", "slots_in_up_x100", "max_outer_up", "job_up_active", ...),
+ * hxv_get_option additionally reports plan statistics ("tile_bits_up", "nblocks_up", "slots_in_up_x100", "max_outer_up", "ncoef_up" / "ncoef_dw" (distinct hopping amplitudes), "job_up_active", ...),
  * driver read-backs ("pass_b_order_last": the phase order the last pass-B launch ran, 1 = out-of-block sums in registers, 0 = the earlier
  * order [eight pairs per thread, row-major scratch patches, a largest block that leaves no room for wt_cols - 1 dead columns, debug bit 8192],
  * -1 = no launch since the plan was made; "lanczos_real_last", "eigh_last_full_passes", "eigh_last_local_passes", "eigh_last_search_products",
