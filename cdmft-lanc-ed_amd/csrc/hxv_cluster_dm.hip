@@ -354,8 +354,6 @@ __global__ void __launch_bounds__(CDM_THREADS) cdm_reduce_kernel(const double2* 
   out[e] = acc;
 }
 
-int nimp_of(const SectorHost& s) { return s.cross.nlat * s.cross.norb; }
-
 // class blocks -> the dense matrix, element (io,jo) at 2*(io + 4^Nimp*jo); weight * raw is rounded before it is added, so that an
 // accumulated matrix equals the sum of the single results bit for bit
 void scatter(const CdmTables& t, const std::vector<double2>& raw, double weight, bool accumulate, double* cdm) {

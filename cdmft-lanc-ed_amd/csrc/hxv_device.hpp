@@ -42,4 +42,20 @@ __device__ __forceinline__ double2 ell_coef(const double2* __restrict__ coef, ui
   return c;
 }
 
+// position of `value` in a sorted sector map (the caller knows it is there)
+__device__ __forceinline__ int rank_in_map(const uint32_t* __restrict__ map, int dim, uint32_t value) {
+  int lo = 0, hi = dim - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (map[mid] < value)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// parity of the occupied orbitals below `pos`: the sign of c / cdg (ED_SETUP.f90:807-833)
+__device__ __forceinline__ int par_below(uint32_t m, int pos) { return __popc(m & ((1u << pos) - 1u)) & 1; }
+
 }  // namespace hxv

@@ -1,5 +1,6 @@
 // The opaque handle behind include/hxv.h and the error helpers shared by the translation units
-// that implement the C-ABI (hxv_capi.hip: handles + products; hxv_lanczos.hip: Lanczos recurrences; hxv_eigh.hip: thick-restart eigensolver).
+// that implement the C-ABI (hxv_capi.hip: handles + products; hxv_lanczos.hip: Lanczos recurrences; hxv_ladder.hip: c / c^dagger between sectors;
+// hxv_eigh.hip: thick-restart eigensolver).
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -53,6 +54,9 @@ int pitch_real_of(const hxv_handle* h);
 // layout conversions between complex [DimDw][pitch] and real [DimDw][pitch_real] device vectors (pads written as zero)
 void launch_to_real(const hxv_handle* h, const double2* src, double* dst, hipStream_t st);
 void launch_to_complex(const hxv_handle* h, const double* src, double2* dst, hipStream_t st);
+// scal[slot] of h->d_scalars = |x|^2 (op 0) or |x| (op 1) of the n double2 elements of x, over all ranks of a split sector, enqueued on the
+// handle's stream (hxv_lanczos.hip)
+int enqueue_norm(hxv_handle* h, const double2* x, int64_t n, int slot, int op);
 // deterministic start vector of this rank's slab (a hash of the global reference index) / its real part
 void launch_init(const hxv_handle* h, double2* q, uint64_t seed, hipStream_t st);
 void launch_init_real(const hxv_handle* h, double* q, uint64_t seed, hipStream_t st);

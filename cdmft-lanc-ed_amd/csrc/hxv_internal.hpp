@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <complex>
 #include <cstdint>
 #include <exception>
@@ -110,6 +111,13 @@ struct SectorHost {
   const std::vector<double>& dev_a_up() const { return row_order() ? a_up_dev : a_up; }
   const std::vector<uint32_t>& dev_nd_up() const { return row_order() ? nd_up_dev : nd_up; }
 };
+// impurity orbitals per spin (the low bits of each spin's configuration, ED_OBSERVABLES.f90:540-556)
+inline int nimp_of(const SectorHost& s) { return s.cross.nlat * s.cross.norb; }
+// position of a bit pattern in a sorted sector map (ED_SETUP.f90:1044-1061 binary_search), -1 if absent
+inline int rank_in(const std::vector<uint32_t>& map, uint32_t m) {
+  auto it = std::lower_bound(map.begin(), map.end(), m);
+  return (it != map.end() && *it == m) ? (int)(it - map.begin()) : -1;
+}
 
 // A host worker thread whose body cannot take the process down: an exception inside the thread -- bad_alloc from the
 // multi-hundred-MB tables of an Ns=18 sector -- would end in std::terminate, and an exception on the CALLING side while the thread is
@@ -205,10 +213,6 @@ struct DevSector {
 // kernel launchers (hxv_kernels.hip)
 struct TilePlan;  // opaque tiling data for the two-pass kernels
 hipError_t launch_hxv_naive(const DevSector& s, const double2* v_full, double2* hv_local, hipStream_t st);
-hipError_t launch_ladder(const uint32_t* map_from, int dim_from, const uint32_t* map_to, int dim_to, int pitch_from, int dimup_to,
-                         int pitch_to, int dimdw_to, int orbital, int spin, int create, const double2* psi, double2* out, hipStream_t st,
-                         double2 coef = double2{1.0, 0.0}, int accumulate = 0, const int32_t* perm_from = nullptr, const uint8_t* sign_from = nullptr,
-                         const uint8_t* sign_to = nullptr);
 // d_out[k*pitch + i] = d_in[cols[k]*pitch + i]: the columns a peer needs, packed for the halo exchange
 struct WtRange;
 // hv(row, c) += the dw part handed over in row ranges (exchange mode 2, overlapped form); hv: [ncols][pitch] elements of double2 or double

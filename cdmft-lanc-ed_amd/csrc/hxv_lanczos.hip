@@ -1,6 +1,7 @@
 // Device Lanczos behind the C-ABI (include/hxv.h): the single-vector recurrences with the SciFortran call shapes
-// (sp_lanc_tridiag, sp_lanc_eigh; ED_GF_NORMAL.f90:215-220, ED_DIAG.f90:176-184), the paired tridiagonalisation, the Green's-function
-// start vectors (c / c^dagger on the ground state, ED_GF_NORMAL.f90:180-199) and the iteration timer of bench.py.
+// (sp_lanc_tridiag, sp_lanc_eigh; ED_GF_NORMAL.f90:215-220, ED_DIAG.f90:176-184), the tridiagonalisation with probe overlaps, the paired
+// tridiagonalisation and the iteration timer of bench.py.  (The Green's-function start vectors, c / c^dagger on the ground state, are
+// hxv_ladder.hip's.)
 // Every driver -- and the local step hxv_eigh_lowest borrows -- takes its fused iteration from ONE function, fused_step_enqueue; the drivers
 // differ in who provides s and c (a host upload, or lz_next on the device), in whether there is a previous vector, and in what they read back.
 #include <algorithm>
@@ -16,17 +17,25 @@ using namespace hxv;
 // ===========================================================================================
 namespace {
 
-// sum of `acc` over the 256 threads of a workgroup (every thread gets it): the LDS tree the one-accumulator reductions end with.  The kernels
-// with two and three accumulators keep their trees written out (one barrier per level for all of them).
-__device__ __forceinline__ double block_sum(double acc) {
-  __shared__ double red[256];
-  red[threadIdx.x] = acc;
+// acc[k] = sum of acc[k] over the 256 threads of a workgroup (every thread gets it), k < N: the LDS tree the reductions end with.  One
+// 256-entry tree per accumulator and one barrier per level for all of them; each sum is added in the order of the single tree, so its bits
+// do not depend on N.
+template <int N>
+__device__ __forceinline__ void block_sum(double (&acc)[N]) {
+  __shared__ double red[N][256];
+  for (int k = 0; k < N; ++k) red[k][threadIdx.x] = acc[k];
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    if ((int)threadIdx.x < s)
+      for (int k = 0; k < N; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
     __syncthreads();
   }
-  return red[0];
+  for (int k = 0; k < N; ++k) acc[k] = red[k][0];
+}
+__device__ __forceinline__ double block_sum(double acc) {
+  double a[1] = {acc};
+  block_sum(a);
+  return a[0];
 }
 
 // w -= b*qm ; partial sums of Re<q,w>
@@ -91,20 +100,11 @@ __global__ void __launch_bounds__(256) lz_sub_nrm_pair(int64_t n, double2* __res
       acc2 = acc2 + t2;
     }
   }
-  __shared__ double red[256], red2[256];
-  red[threadIdx.x] = acc;
-  red2[threadIdx.x] = acc2;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      red[threadIdx.x] += red[threadIdx.x + s];
-      red2[threadIdx.x] += red2[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
+  double sum[2] = {acc, acc2};
+  block_sum(sum);
   if (threadIdx.x == 0) {
-    partial_a[blockIdx.x] = red[0];
-    partial_b[blockIdx.x] = red2[0];
+    partial_a[blockIdx.x] = sum[0];
+    partial_b[blockIdx.x] = sum[1];
   }
 }
 
@@ -124,20 +124,12 @@ __global__ void __launch_bounds__(256) lz_pack_pair(int64_t n, const double2* __
       nb = nb + t2;
     }
   }
-  __shared__ double red[3][256];
-  red[0][threadIdx.x] = im;
-  red[1][threadIdx.x] = na;
-  red[2][threadIdx.x] = nb;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-      for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-    __syncthreads();
-  }
+  double sum[3] = {im, na, nb};
+  block_sum(sum);
   if (threadIdx.x == 0) {
-    p_im[blockIdx.x] = red[0][0];
-    p_a[blockIdx.x] = red[1][0];
-    p_b[blockIdx.x] = red[2][0];
+    p_im[blockIdx.x] = sum[0];
+    p_a[blockIdx.x] = sum[1];
+    p_b[blockIdx.x] = sum[2];
   }
 }
 
@@ -236,7 +228,16 @@ __global__ void __launch_bounds__(256) lz_axpy(int64_t n, double2* __restrict__ 
   }
 }
 
-// deterministic start vector: splitmix64 hash of the global index -> uniform(-0.5,0.5) re and im
+// splitmix64 hash of x -> uniform(-0.5,0.5)
+__device__ __forceinline__ double lz_uniform(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  x = x ^ (x >> 31);
+  return (double)(x >> 11) * (1.0 / 9007199254740992.0) - 0.5;
+}
+
+// deterministic start vector: the hash of the global index -> re and im
 // (col0 = first global column of this rank's slab: a split sector starts from the same global vector as the unsplit one)
 // (device row order, SectorHost::up_perm: the vector is defined on the REFERENCE index -- device row `row` holds reference row iperm[row],
 //  times its basis sign -- so a sector starts from the same vector whatever order its rows are stored in)
@@ -252,16 +253,8 @@ __global__ void __launch_bounds__(256) lz_init(int64_t n, double2* __restrict__ 
     }
     const int rrow = iperm ? iperm[row] : row;
     const double sgn = (sign && sign[row]) ? -1.0 : 1.0;
-    uint64_t z = (uint64_t)(col * dimup + rrow) * 2 + seed;
-    double r[2];
-    for (int k = 0; k < 2; ++k) {
-      uint64_t x = z + (uint64_t)k + 0x9E3779B97F4A7C15ull;
-      x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-      x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-      x = x ^ (x >> 31);
-      r[k] = (double)(x >> 11) * (1.0 / 9007199254740992.0) - 0.5;
-    }
-    q[i] = make_double2(sgn * r[0], sgn * r[1]);
+    const uint64_t z = (uint64_t)(col * dimup + rrow) * 2 + seed;
+    q[i] = make_double2(sgn * lz_uniform(z), sgn * lz_uniform(z + 1));
   }
 }
 
@@ -311,11 +304,7 @@ __global__ void __launch_bounds__(256) lz_init_real(int64_t n, double* __restric
       continue;
     }
     const int rrow = iperm ? iperm[row] : row;
-    uint64_t x = (uint64_t)(col * dimup + rrow) * 2 + seed + 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    x = x ^ (x >> 31);
-    const double r = (double)(x >> 11) * (1.0 / 9007199254740992.0) - 0.5;
+    const double r = lz_uniform((uint64_t)(col * dimup + rrow) * 2 + seed);
     q[i] = (sign && sign[row]) ? -r : r;
   }
 }
@@ -392,12 +381,6 @@ int reduce_scalar(hxv_handle* h, const double* partial, int np, int io, int op, 
   return HXV_OK;
 }
 
-// scal[slot] = |x|^2 (op 0) or |x| (op 1) of the n double2 elements of x, over all ranks of a split sector
-int enqueue_norm(hxv_handle* h, const double2* x, int64_t n, int slot, int op) {
-  const int g = grid_for(n);
-  hipLaunchKernelGGL(lz_nrm, dim3(g), dim3(256), 0, h->stream, n, x, h->d_partials + RED_BLOCKS);
-  return reduce_scalar(h, h->d_partials + RED_BLOCKS, g, slot, op);
-}
 // q = w / |w|   (q may be w); the norm stays in scal[slot]
 int enqueue_normalise(hxv_handle* h, double2* q, const double2* w, int64_t n, int slot) {
   int rc = enqueue_norm(h, w, n, slot, 1);
@@ -468,6 +451,10 @@ int fused_step_enqueue(hxv_handle* h, bool real, const double2* q, const double2
   return rc;
 }
 
+// The norm a recurrence starts from.  SciFortran's sp_lanc_tridiag normalises vin on its first iteration; the reference's call sites pass a
+// normalised vector already (ED_GF_NORMAL.f90:197-199): a measured norm that is 1 to rounding is taken as exactly 1.
+inline double start_norm(double nrm) { return std::fabs(nrm - 1.0) <= 1e-14 ? 1.0 : nrm; }
+
 // The host's copy of one component's scale factors in the fused recurrence: the stored vector X_k times s_cur = 1/beta_k is the unit Lanczos
 // vector, beta_prev = beta_{k-1} (the start vector's norm is carried as beta_0).
 struct LzScale {
@@ -502,6 +489,15 @@ __global__ void lz_next(double* scal, double* alpha_out, double* beta_out, int n
 struct LzBuf {
   double2 *q, *qm, *w;
 };
+// a small device array of one driver call (hipMalloc'ed into p by the driver): freed on every way out, after the stream has drained
+struct DevFree {
+  hipStream_t st;
+  double* p = nullptr;
+  ~DevFree() {
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(p);
+  }
+};
 
 // Lanczos recurrence on device.  Two implementations of one step:
 //  * plain : w = H q (any kernel), then lz_sub_dot / lz_sub_nrm / lz_scale on normalised vectors;
@@ -528,6 +524,17 @@ struct LzRunner {
     sc.begin(nrm);
     if (!fused && nrm != 1.0) return fail(HXV_ERR_STATE, "plain Lanczos expects a normalised start vector");
     return HXV_OK;
+  }
+
+  // The library's own start vector: the deterministic one of `seed` in the run's layout (built in b.w), normalised into b.q; clears the scalars
+  int begin_own(uint64_t seed) {
+    if (real)
+      launch_init_real(h, (double*)b.w, seed, h->stream);
+    else
+      launch_init(h, b.w, seed, h->stream);
+    HIPCHK(hipMemsetAsync(h->d_scalars, 0, 8 * sizeof(double), h->stream));
+    int rc = enqueue_normalise(h, b.q, b.w, n2, LZ_BETA);
+    return rc ? rc : begin(1.0);
   }
 
   int step(double* alpha, double* beta) {
@@ -558,23 +565,11 @@ struct LzRunner {
     return HXV_OK;
   }
 
-  // Hand-over from iteration 0 (done by step(), which returned `beta`) to the device-only iterations: the scalars of iteration 1 and the
-  // step counter go to device memory, where lz_next keeps them from then on.
-  hipError_t begin_device_iterations(double beta) {
-    const double s1 = 1.0 / beta, bprev = 1.0 / sc.s_cur;
-    const double init[2] = {s1, 1.0 / (s1 * bprev)};   // s_1 = 1/beta_1 ; c_1 = beta_1/beta_0, rounded like LzScale::next() + c()
-    const double one = 1.0;
-    hipError_t e = hipMemcpyAsync(h->d_scalars + LZ_S, init, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->d_scalars + LZ_STEP, &one, sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (init and one are read by asynchronous copies)
-    return e;
-  }
-
-  // Iterations 1..nmax-1 of a fixed-length run on the device alone (after begin_device_iterations): each one is the fused step on the
+  // Iterations 1..nmax-1 of a fixed-length run on the device alone (after the hand-over of run_device_only): each one is the fused step on the
   // scalars lz_next left, then lz_next; alpha/beta go to device arrays.  The three-iteration pointer-rotation cycle is captured ONCE into a
   // hipGraph and replayed, so a small sector pays one graph launch per three iterations instead of ~9 kernel launches, two copies and a
   // synchronisation per iteration.  Leaves b.q/b.qm/b.w as after the last iteration.
-  int run_device_iterations(int nmax, double* d_alpha, double* d_beta, bool use_graph) {
+  int run_device_iterations(int nmax, double* d_alpha, double* d_beta) {
     double2* buf[3] = {b.q, b.w, b.qm};  // iteration k uses q = buf[k%3] (k counted from 1: q = former w), w = buf[(k+1)%3], qm = buf[(k+2)%3]
     // after step() of iteration 0 and before any rotation: X_1 = b.w, X_0 = b.q, free = b.qm
     int k = 1;
@@ -584,7 +579,7 @@ struct LzRunner {
       hipLaunchKernelGGL(lz_next, dim3(1), dim3(1), 0, h->stream, h->d_scalars, d_alpha, d_beta, nmax);
       return HXV_OK;
     };
-    const int cycles = use_graph ? (nmax - 1) / 3 : 0;
+    const int cycles = (nmax - 1) / 3;
     if (cycles >= 2) {
       hipGraph_t graph = nullptr;
       hipGraphExec_t exec = nullptr;
@@ -619,6 +614,38 @@ struct LzRunner {
     b.w = buf[nmax % 3];
     b.qm = buf[(nmax + 1) % 3];
     first = false;
+    return HXV_OK;
+  }
+
+  // The whole device-only run after step() of iteration 0 returned `beta`: the device arrays of alpha and beta (nmax each, zeroed, freed on
+  // every way out), the hand-over -- the scalars of iteration 1 and the step counter go to device memory, where lz_next keeps them from then
+  // on --, iterations 1..nmax-1 three per hipGraph.  ab (may be null): 2*nmax host doubles that receive the two arrays.  ev (may be null:
+  // hxv_time_lanczos's pair): ev[0] is recorded after the hand-over and before the first captured iteration, ev[1]
+  // after the last one, and waited for.
+  int run_device_only(double beta, int nmax, double* ab, hipEvent_t* ev, const char* who) {
+    DevFree d_ab{h->stream};
+    HIPCHK(hipMalloc((void**)&d_ab.p, (size_t)2 * nmax * sizeof(double)));
+    HIPCHK(hipMemsetAsync(d_ab.p, 0, (size_t)2 * nmax * sizeof(double), h->stream));
+    const double s1 = 1.0 / beta, bprev = 1.0 / sc.s_cur;
+    const double init[2] = {s1, 1.0 / (s1 * bprev)};   // s_1 = 1/beta_1 ; c_1 = beta_1/beta_0, rounded like LzScale::next() + c()
+    const double one = 1.0;
+    hipError_t e = hipMemcpyAsync(h->d_scalars + LZ_S, init, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->d_scalars + LZ_STEP, &one, sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (init and one are read by asynchronous copies)
+    if (e == hipSuccess && ev) e = hipEventRecord(ev[0], h->stream);
+    if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    int rc = run_device_iterations(nmax, d_ab.p, d_ab.p + nmax);
+    if (rc) return rc;
+    if (ev) {
+      e = hipEventRecord(ev[1], h->stream);
+      if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+      if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    if (ab) {
+      e = hipMemcpyAsync(ab, d_ab.p, (size_t)2 * nmax * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+      if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string("reading alpha/beta back: ") + hipGetErrorString(e));
+    }
     return HXV_OK;
   }
 
@@ -678,29 +705,33 @@ int ensure_lz(hxv_handle* h, bool real) {
   return HXV_OK;
 }
 
-// A start vector that lives in one of the handle's gather buffers (built at hxv_slab_home) would be zeroed by ensure_lz, which clears the
-// slab's place in all three before the driver reads its input: such a vector is copied to a staging slab first (one slab copy per RUN).
-// *tmp is the staging buffer to pool_free after the run, or null.
-int stage_start_vector(hxv_handle* h, const void*& d_vin, double2** tmp) {
-  *tmp = nullptr;
-  if (!comm_ready(h) || !comm_in_gather(h, d_vin)) return HXV_OK;
-  const size_t bytes = (size_t)h->host.pitch * std::max(h->host.qdw, 1) * sizeof(double2);
-  HIPCHK(pool_alloc(h->device, bytes, (void**)tmp));
-  HIPCHK(hipMemcpyAsync(*tmp, d_vin, bytes, hipMemcpyDeviceToDevice, h->stream));
-  d_vin = *tmp;
-  return HXV_OK;
-}
-struct StageFree {
+// What a driver call took from the device-buffer cache goes back to it when the call returns, after the stream has drained.
+struct PoolGuard {
   hxv_handle* h;
-  double2* p[2];
-  ~StageFree() {
-    for (double2* q : p)
-      if (q) {
-        (void)hipStreamSynchronize(h->stream);
-        pool_free(h->device, q);
-      }
+  std::vector<void*> p;
+  int take(size_t bytes, void** out) {
+    HIPCHK(pool_alloc(h->device, bytes, out));
+    p.push_back(*out);
+    return HXV_OK;
+  }
+  ~PoolGuard() {
+    if (!p.empty()) (void)hipStreamSynchronize(h->stream);
+    for (void* q : p) pool_free(h->device, q);
   }
 };
+
+// A start vector that lives in one of the handle's gather buffers (built at hxv_slab_home) would be zeroed by ensure_lz, which clears the
+// slab's place in all three before the driver reads its input: such a vector is copied to a staging slab first (one slab copy per RUN).
+// The staging buffer goes into `pooled`, which returns it after the run.
+int stage_start_vector(hxv_handle* h, const void*& d_vin, PoolGuard& pooled) {
+  if (!comm_ready(h) || !comm_in_gather(h, d_vin)) return HXV_OK;
+  const size_t bytes = (size_t)h->host.pitch * std::max(h->host.qdw, 1) * sizeof(double2);
+  void* tmp = nullptr;
+  if (int rc = pooled.take(bytes, &tmp)) return rc;
+  HIPCHK(hipMemcpyAsync(tmp, d_vin, bytes, hipMemcpyDeviceToDevice, h->stream));
+  d_vin = tmp;
+  return HXV_OK;
+}
 
 // out[2*j], out[2*j+1] = Re, Im <p_j|x> of this rank's share (n double2 elements), j < m: one pass over x and the probes, then one workgroup
 // that adds the block partials in block order.  d_part: grid_for(n) * 2m doubles.
@@ -728,6 +759,12 @@ void launch_probe_dots(hxv_handle* h, int m, int64_t n, const double2* x, const 
 }  // namespace
 
 namespace hxv {
+// scal[slot] = |x|^2 (op 0) or |x| (op 1) of the n double2 elements of x, over all ranks of a split sector
+int enqueue_norm(hxv_handle* h, const double2* x, int64_t n, int slot, int op) {
+  const int g = grid_for(n);
+  hipLaunchKernelGGL(lz_nrm, dim3(g), dim3(256), 0, h->stream, n, x, h->d_partials + RED_BLOCKS);
+  return reduce_scalar(h, h->d_partials + RED_BLOCKS, g, slot, op);
+}
 void launch_to_real(const hxv_handle* h, const double2* src, double* dst, hipStream_t st) {
   const int pr = pitch_real_of(h);
   hipLaunchKernelGGL(lz_to_real, dim3(grid_for((int64_t)pr * h->host.qdw)), dim3(256), 0, st, h->host.dimup, h->host.qdw, h->host.pitch, pr,
@@ -777,157 +814,26 @@ void launch_init_real(const hxv_handle* h, double* q, uint64_t seed, hipStream_t
 }
 }  // namespace hxv
 
-extern "C" {
-
-int hxv_lanczos_tridiag(hxv_handle* h, const void* d_vin, int32_t nlanc, double* alanc, double* blanc, double threshold,
-                        int32_t* nsteps) {
-  if (!h) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag: NULL handle");
+namespace {
+// THE tridiagonalisation driver behind hxv_lanczos_tridiag (nprobes = 0) and hxv_lanczos_tridiag_probes: start-up, then the host-stepped loop
+// with the overlaps <p_j|q_k> of every Lanczos vector collected on the way, or -- a fixed-length run without probes on a serial sector -- the
+// device-only run.  who: the entry's name, for the messages.  rc_args: what the entry decided from its own arguments; it goes INTO the first
+// agreement (split sector: a rank whose arguments are bad tells its peers instead of leaving them in the first all-reduce), so nothing here
+// looks at an argument before that agreement.  Collectives of a split sector: agree, the all-reduce of the real check when one is made, agree.
+int tridiag_run(hxv_handle* h, const char* who, int rc_args, const void* d_vin, int nprobes, const void* const* d_probes, int nlanc,
+                double* alanc, double* blanc, double* overlaps, double threshold, int32_t* nsteps) {
   HIPCHK(hipSetDevice(h->device));  // (before the first collective: thread ranks on several GPUs each have their own current device)
-  // (split sector: a rank whose arguments are bad tells its peers instead of leaving them in the first all-reduce)
-  if (int rca = comm_agree(h, (!d_vin || nlanc < 1 || !alanc || !blanc) ? fail(HXV_ERR_ARG, "hxv_lanczos_tridiag: bad argument") : HXV_OK)) return rca;
-  const int64_t n = (int64_t)h->host.pitch * h->host.qdw;  // this rank's slab
-  StageFree staged{h, {nullptr, nullptr}};
-  // REAL-vector mode: H real and the start vector purely real (c / c^dagger applied to a real ground state is) ->
-  // the whole recurrence stays real; alanc/blanc are the same numbers at half the bytes per pass
-  bool real = want_real(h);
-  int rc_pre = HXV_OK;
-  if (int rcc = need_comm(h, "device Lanczos")) return rcc;
-  if (real) {  // sum of Im(vin)^2 over ALL ranks (dst = null: reduction only): every rank must take the same path
-    const int pr = pitch_real_of(h);
-    const int g = grid_for((int64_t)pr * h->host.qdw);
-    hipLaunchKernelGGL(lz_to_real, dim3(g), dim3(256), 0, h->stream, h->host.dimup, h->host.qdw, h->host.pitch, pr,
-                       (const double2*)d_vin, (double*)nullptr, h->d_partials);
-    // (a rank that fails here must still meet its peers in the agreement below, not leave them there: ADVICE r4)
-    rc_pre = reduce_scalar(h, h->d_partials, g, LZ_TMP, 0);
-    double im2 = 0.0;
-    if (!rc_pre && hipMemcpyAsync(&im2, h->d_scalars + LZ_TMP, sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc_pre = fail(HXV_ERR_HIP, "hxv_lanczos_tridiag: reading the real-vector check failed");
-    if (!rc_pre && hipStreamSynchronize(h->stream) != hipSuccess) rc_pre = fail(HXV_ERR_HIP, "hxv_lanczos_tridiag: the real-vector check failed");
-    real = im2 == 0.0;
-  }
-  int rc = rc_pre ? rc_pre : stage_start_vector(h, d_vin, &staged.p[0]);  // (a start vector at hxv_slab_home: staged before its home is cleared)
-  rc = comm_agree(h, rc ? rc : ensure_lz(h, real));  // (a rank that could not allocate tells its peers before the first all-reduce)
-  if (rc) return rc;
-  LzRunner lz(h, h->lz_vec[0], h->lz_vec[1], h->lz_vec[2], real);
-  if (real)
-    launch_to_real(h, (const double2*)d_vin, (double*)lz.b.q, h->stream);
-  else
-    HIPCHK(hipMemcpyAsync(lz.b.q, d_vin, (size_t)n * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
-  // SciFortran's sp_lanc_tridiag normalises vin on its first iteration; the reference's call sites pass a normalised
-  // vector already (ED_GF_NORMAL.f90:197-199).  Measure the (global) norm and normalise only when it is not 1.
-  {
-    rc = enqueue_norm(h, lz.b.q, lz.n2, LZ_TMP, 1);
-    if (rc) return rc;
-    double nrm = 0.0;
-    HIPCHK(hipMemcpyAsync(&nrm, h->d_scalars + LZ_TMP, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (!(nrm > 0.0) || !std::isfinite(nrm)) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag: the start vector is zero or not finite");
-    if (std::fabs(nrm - 1.0) <= 1e-14) {
-      rc = lz.begin(1.0);
-    } else if (lz.fused) {
-      rc = lz.begin(nrm);  // the fused recurrence carries the scale factor
-    } else {
-      hipLaunchKernelGGL(lz_scale, dim3(grid_for(lz.n2)), dim3(256), 0, h->stream, lz.n2, lz.b.q, lz.b.q, h->d_scalars, LZ_TMP);
-      rc = lz.begin(1.0);
-    }
-  }
-  if (rc) return rc;
-  for (int k = 0; k < nlanc; ++k) {
-    alanc[k] = 0;
-    blanc[k] = 0;
-  }
-  int k = 0;
-  if (lz.fused && h->lz_graph && nlanc >= 8 && !comm_ready(h)) {  // (device-only iterations: serial sectors; the all-reduces of a split one go through the host loop)
-    // Fixed-length run (the Green's-function use, ED_GF_NORMAL.f90:204-220): iteration 0 with the host in the loop, the
-    // other nlanc-1 on the device alone -- scalars stay in device memory, the pointer-rotation cycle of three
-    // iterations is one hipGraph -- and alpha/beta come back once at the end.  A breakdown (beta < threshold) is
-    // found afterwards; whatever was computed past it is discarded.
-    double a, bt;
-    rc = lz.step(&a, &bt);
-    if (rc) return rc;
-    alanc[0] = a;
-    blanc[1] = bt;
-    k = 1;
-    if (std::fabs(bt) >= threshold) {
-      double* d_ab = nullptr;
-      HIPCHK(hipMalloc((void**)&d_ab, (size_t)2 * nlanc * sizeof(double)));
-      HIPCHK(hipMemsetAsync(d_ab, 0, (size_t)2 * nlanc * sizeof(double), h->stream));
-      rc = lz.begin_device_iterations(bt) != hipSuccess ? fail(HXV_ERR_HIP, "scalar upload failed") : lz.run_device_iterations(nlanc, d_ab, d_ab + nlanc, true);
-      std::vector<double> ab((size_t)2 * nlanc, 0.0);
-      if (rc == HXV_OK) {
-        hipError_t e3 = hipMemcpyAsync(ab.data(), d_ab, ab.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-        if (e3 == hipSuccess) e3 = hipStreamSynchronize(h->stream);
-        if (e3 != hipSuccess) rc = fail(HXV_ERR_HIP, std::string("reading alpha/beta back: ") + hipGetErrorString(e3));
-      }
-      (void)hipStreamSynchronize(h->stream);
-      (void)hipFree(d_ab);
-      if (rc) return rc;
-      for (k = 1; k < nlanc; ++k) {
-        alanc[k] = ab[k];
-        const double b1 = k + 1 < nlanc ? ab[(size_t)nlanc + k + 1] : 1.0;
-        if (k + 1 < nlanc) blanc[k + 1] = b1;
-        if (!std::isfinite(alanc[k]) || !std::isfinite(b1) || (k + 1 < nlanc && std::fabs(b1) < threshold)) {
-          if (!std::isfinite(alanc[k])) alanc[k] = 0.0;
-          if (k + 1 < nlanc && !std::isfinite(b1)) blanc[k + 1] = 0.0;
-          ++k;
-          break;
-        }
-      }
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (nsteps) *nsteps = k;
-    return HXV_OK;
-  }
-  for (; k < nlanc; ++k) {
-    double a, bt;
-    rc = lz.step(&a, &bt);
-    if (rc) return rc;
-    alanc[k] = a;
-    if (k + 1 < nlanc) blanc[k + 1] = bt;
-    if (std::fabs(bt) < threshold) {
-      ++k;
-      break;
-    }
-    if (k + 1 < nlanc) {
-      rc = lz.advance();
-      if (rc) return rc;
-    }
-  }
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (nsteps) *nsteps = k;
-  return HXV_OK;
-}
-
-// hxv_lanczos_tridiag's host-stepped loop with the overlaps <p_j|q_k> of every Lanczos vector collected on the way (include/hxv.h): the
-// off-diagonal Green's functions G_ij of one orbital i from ONE run instead of the reference's mixed channels (ED_GF_NORMAL.f90:315-903).
-int hxv_lanczos_tridiag_probes(hxv_handle* h, const void* d_vin, int32_t nprobes, const void* const* d_probes, int32_t nlanc, double* alanc,
-                               double* blanc, double* overlaps, double threshold, int32_t* nsteps) {
-  if (!h) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: NULL handle");
-  HIPCHK(hipSetDevice(h->device));  // (before the first collective)
-  // scratch of the run, from the device-buffer cache and sized by nprobes: block partials of the real-vector check (start vector and probes, side
-  // by side), block partials and sums of a step's overlaps
+  // scratch of a run WITH probes, from the device-buffer cache and sized by nprobes: block partials of the real-vector check (start vector and
+  // probes, side by side), block partials and sums of a step's overlaps.  Without probes the check's partials are the handle's own.
   double* d_ws = nullptr;
-  struct Free {
-    hxv_handle* h;
-    double*& p;
-    ~Free() {
-      if (!p) return;
-      (void)hipStreamSynchronize(h->stream);
-      pool_free(h->device, p);
-    }
-  } guard{h, d_ws};
-  const int np1 = std::max(1, std::min<int>(nprobes, HXV_MAX_PROBES));
-  const size_t n_chk = (size_t)(1 + np1) * RED_BLOCKS, n_part = (size_t)2 * np1 * RED_BLOCKS;
+  PoolGuard pooled{h, {}};  // (with the staged start vector and the real-mode copies of the probes)
+  size_t n_chk = 0, n_part = 0;
   // what a rank decides from its own arguments and resources, agreed on before the first collective
-  auto check_args = [&]() -> int {
-    if (!d_vin || nlanc < 1 || !alanc || !blanc || !nsteps) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: bad argument (NULL start vector or output, or nlanc < 1)");
-    if (nprobes < 0 || nprobes > HXV_MAX_PROBES) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: nprobes must be 0 .. HXV_MAX_PROBES (8)");
-    if (nprobes > 0 && (!d_probes || !overlaps)) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: nprobes > 0 needs the probe list and the overlaps array");
-    for (int j = 0; j < nprobes; ++j) {
-      if (!d_probes[j]) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: NULL entry in the probe list");
-      // (ensure_lz clears the slab's place in the gather buffers; a START vector there is staged, a probe is the caller's to keep elsewhere)
-      if (comm_ready(h) && comm_in_gather(h, d_probes[j])) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: a probe lies in a gather buffer of the handle (hxv_slab_home): the driver clears that place");
-    }
-    HIPCHK(pool_alloc(h->device, (n_chk + n_part + 2 * np1) * sizeof(double), (void**)&d_ws));
+  auto resources = [&]() -> int {
+    if (rc_args || nprobes == 0) return rc_args;
+    n_chk = (size_t)(1 + nprobes) * RED_BLOCKS;
+    n_part = (size_t)2 * nprobes * RED_BLOCKS;
+    if (int rc = pooled.take((n_chk + n_part + 2 * nprobes) * sizeof(double), (void**)&d_ws)) return rc;
     // page-locked staging for the overlaps of every step: a copy into the caller's pageable array could make the runtime wait per step
     const int64_t want = (int64_t)2 * nprobes * nlanc;
     if (want > h->probe_ov_n) {
@@ -939,26 +845,15 @@ int hxv_lanczos_tridiag_probes(hxv_handle* h, const void* d_vin, int32_t nprobes
     }
     return HXV_OK;
   };
-  if (int rca = comm_agree(h, check_args())) return rca;
+  if (int rca = comm_agree(h, resources())) return rca;
   if (int rcc = need_comm(h, "device Lanczos")) return rcc;
-  double *d_part = d_ws + n_chk, *d_ov = d_part + n_part;
+  double *d_chk = nprobes ? d_ws : h->d_partials, *d_part = d_ws + n_chk, *d_ov = d_part + n_part;
   const int64_t n = (int64_t)h->host.pitch * h->host.qdw;  // this rank's slab
   const size_t real_bytes = (size_t)pitch_real_of(h) * std::max(h->host.qdw, 1) * sizeof(double);
-  StageFree staged{h, {nullptr, nullptr}};
   double* real_probe[HXV_MAX_PROBES] = {};
-  struct FreeProbes {  // the real-mode copies of the probes go back to the buffer cache before the call returns
-    hxv_handle* h;
-    double** p;
-    ~FreeProbes() {
-      bool any = false;
-      for (int j = 0; j < HXV_MAX_PROBES; ++j) any = any || p[j];
-      if (any) (void)hipStreamSynchronize(h->stream);
-      for (int j = 0; j < HXV_MAX_PROBES; ++j)
-        if (p[j]) pool_free(h->device, p[j]);
-    }
-  } probe_guard{h, real_probe};
-  // REAL-vector mode under hxv_lanczos_tridiag's rule, AND every probe purely real: the sum of Im^2 over the start vector and the probes, over
-  // all ranks, in ONE reduction (every rank must take the same path)
+  // REAL-vector mode: H real and the start vector purely real (c / c^dagger applied to a real ground state is) AND every probe purely real ->
+  // the whole recurrence stays real; alanc/blanc are the same numbers at half the bytes per pass.  The sum of Im^2 over the start vector and
+  // the probes, over ALL ranks, in ONE reduction (dst = null: reduction only): every rank must take the same path
   bool real = want_real(h);
   int rc_pre = HXV_OK;
   if (real) {
@@ -966,20 +861,20 @@ int hxv_lanczos_tridiag_probes(hxv_handle* h, const void* d_vin, int32_t nprobes
     const int g = grid_for((int64_t)pr * h->host.qdw);
     for (int j = 0; j <= nprobes; ++j)
       hipLaunchKernelGGL(lz_to_real, dim3(g), dim3(256), 0, h->stream, h->host.dimup, h->host.qdw, h->host.pitch, pr,
-                         (const double2*)(j ? d_probes[j - 1] : d_vin), (double*)nullptr, d_ws + (size_t)j * g);
-    rc_pre = reduce_scalar(h, d_ws, (1 + nprobes) * g, LZ_TMP, 0);
+                         (const double2*)(j ? d_probes[j - 1] : d_vin), (double*)nullptr, d_chk + (size_t)j * g);
+    // (a rank that fails here must still meet its peers in the agreement below, not leave them there: ADVICE r4)
+    rc_pre = reduce_scalar(h, d_chk, (1 + nprobes) * g, LZ_TMP, 0);
     double im2 = 0.0;
-    if (!rc_pre && hipMemcpyAsync(&im2, h->d_scalars + LZ_TMP, sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc_pre = fail(HXV_ERR_HIP, "hxv_lanczos_tridiag_probes: reading the real-vector check failed");
-    if (!rc_pre && hipStreamSynchronize(h->stream) != hipSuccess) rc_pre = fail(HXV_ERR_HIP, "hxv_lanczos_tridiag_probes: the real-vector check failed");
+    if (!rc_pre && hipMemcpyAsync(&im2, h->d_scalars + LZ_TMP, sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc_pre = fail(HXV_ERR_HIP, std::string(who) + ": reading the real-vector check failed");
+    if (!rc_pre && hipStreamSynchronize(h->stream) != hipSuccess) rc_pre = fail(HXV_ERR_HIP, std::string(who) + ": the real-vector check failed");
     real = im2 == 0.0;
   }
   auto prepare = [&]() -> int {
     if (rc_pre) return rc_pre;
-    int r = stage_start_vector(h, d_vin, &staged.p[0]);  // (a start vector at hxv_slab_home: staged before its home is cleared)
+    int r = stage_start_vector(h, d_vin, pooled);  // (a start vector at hxv_slab_home: staged before its home is cleared)
     if (!r) r = ensure_lz(h, real);
-    if (r) return r;
-    for (int j = 0; real && j < nprobes; ++j) HIPCHK(pool_alloc(h->device, real_bytes, (void**)&real_probe[j]));
-    return HXV_OK;
+    for (int j = 0; real && j < nprobes && !r; ++j) r = pooled.take(real_bytes, (void**)&real_probe[j]);
+    return r;
   };
   int rc = comm_agree(h, prepare());  // (a rank that could not allocate tells its peers before the first all-reduce)
   if (rc) return rc;
@@ -993,59 +888,111 @@ int hxv_lanczos_tridiag_probes(hxv_handle* h, const void* d_vin, int32_t nprobes
     launch_to_real(h, (const double2*)d_vin, (double*)lz.b.q, h->stream);
   else
     HIPCHK(hipMemcpyAsync(lz.b.q, d_vin, (size_t)n * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
-  {  // the start vector's norm, as in hxv_lanczos_tridiag
+  {  // measure the (global) norm and normalise only when it is not 1 (start_norm)
     rc = enqueue_norm(h, lz.b.q, lz.n2, LZ_TMP, 1);
     if (rc) return rc;
     double nrm = 0.0;
     HIPCHK(hipMemcpyAsync(&nrm, h->d_scalars + LZ_TMP, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (!(nrm > 0.0) || !std::isfinite(nrm)) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: the start vector is zero or not finite");
-    if (std::fabs(nrm - 1.0) <= 1e-14) {
-      rc = lz.begin(1.0);
-    } else if (lz.fused) {
-      rc = lz.begin(nrm);
-    } else {
+    if (!(nrm > 0.0) || !std::isfinite(nrm)) return fail(HXV_ERR_ARG, std::string(who) + ": the start vector is zero or not finite");
+    nrm = start_norm(nrm);
+    if (nrm != 1.0 && !lz.fused) {  // (the fused recurrence carries the scale factor; the plain one wants a unit vector)
       hipLaunchKernelGGL(lz_scale, dim3(grid_for(lz.n2)), dim3(256), 0, h->stream, lz.n2, lz.b.q, lz.b.q, h->d_scalars, LZ_TMP);
-      rc = lz.begin(1.0);
+      nrm = 1.0;
     }
+    rc = lz.begin(nrm);
   }
   if (rc) return rc;
   for (int k = 0; k < nlanc; ++k) alanc[k] = blanc[k] = 0.0;
   for (size_t i = 0; i < (size_t)2 * nlanc * nprobes; ++i) overlaps[i] = 0.0;
   int k = 0;
-  for (; k < nlanc; ++k) {
-    double* ov = nprobes > 0 ? overlaps + (size_t)2 * nprobes * k : nullptr;
-    double* stage = nprobes > 0 ? h->h_probe_ov + (size_t)2 * nprobes * k : nullptr;  // (a slot per step: nothing is overwritten while a copy is in flight)
-    if (nprobes > 0) {
-      // the overlaps of the STORED vector X_k, enqueued before the step that overwrites nothing of it; their copy to the host completes with
-      // the synchronisation step() makes for alpha and beta.  One all-reduce for the 2*nprobes sums of a split sector.
-      if (real)
-        launch_probe_dots<true>(h, nprobes, lz.n2, lz.vec(), pr, d_part, d_ov);
-      else
-        launch_probe_dots<false>(h, nprobes, lz.n2, lz.vec(), pr, d_part, d_ov);
-      rc = comm_allreduce_sum(h, d_ov, (size_t)2 * nprobes, h->stream);
-      if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(stage, d_ov, (size_t)2 * nprobes * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    }
-    const double s = lz.scale();  // q_k = s * X_k
-    double a, bt;
-    rc = lz.step(&a, &bt);
+  if (nprobes == 0 && lz.fused && h->lz_graph && nlanc >= 8 && !comm_ready(h)) {  // (device-only iterations: serial sectors; the all-reduces of a split one go through the host loop)
+    // Fixed-length run without probes (the Green's-function use, ED_GF_NORMAL.f90:204-220): iteration 0 with the host in the loop, the other
+    // nlanc-1 on the device alone -- scalars stay in device memory, the pointer-rotation cycle of three iterations is one hipGraph -- and
+    // alpha/beta come back once at the end.  A breakdown (beta < threshold) is found afterwards; whatever was computed past it is discarded.
+    rc = lz.step(&alanc[0], &blanc[1]);
     if (rc) return rc;
-    for (int j = 0; j < 2 * nprobes; ++j) ov[j] = stage[j] * s;
-    alanc[k] = a;
-    if (k + 1 < nlanc) blanc[k + 1] = bt;
-    if (std::fabs(bt) < threshold) {
-      ++k;
-      break;
-    }
-    if (k + 1 < nlanc) {
-      rc = lz.advance();
+    k = 1;
+    if (std::fabs(blanc[1]) >= threshold) {
+      std::vector<double> ab((size_t)2 * nlanc, 0.0);
+      rc = lz.run_device_only(blanc[1], nlanc, ab.data(), nullptr, who);
       if (rc) return rc;
+      for (; k < nlanc; ++k) {
+        alanc[k] = ab[k];
+        const double b1 = k + 1 < nlanc ? ab[(size_t)nlanc + k + 1] : 1.0;
+        if (k + 1 < nlanc) blanc[k + 1] = b1;
+        if (!std::isfinite(alanc[k]) || !std::isfinite(b1) || (k + 1 < nlanc && std::fabs(b1) < threshold)) {
+          if (!std::isfinite(alanc[k])) alanc[k] = 0.0;
+          if (k + 1 < nlanc && !std::isfinite(b1)) blanc[k + 1] = 0.0;
+          ++k;
+          break;
+        }
+      }
+    }
+  } else {
+    for (; k < nlanc; ++k) {
+      double* ov = nprobes > 0 ? overlaps + (size_t)2 * nprobes * k : nullptr;
+      double* stage = nprobes > 0 ? h->h_probe_ov + (size_t)2 * nprobes * k : nullptr;  // (a slot per step: nothing is overwritten while a copy is in flight)
+      if (nprobes > 0) {
+        // the overlaps of the STORED vector X_k, enqueued before the step that overwrites nothing of it; their copy to the host completes with
+        // the synchronisation step() makes for alpha and beta.  One all-reduce for the 2*nprobes sums of a split sector.
+        if (real)
+          launch_probe_dots<true>(h, nprobes, lz.n2, lz.vec(), pr, d_part, d_ov);
+        else
+          launch_probe_dots<false>(h, nprobes, lz.n2, lz.vec(), pr, d_part, d_ov);
+        rc = comm_allreduce_sum(h, d_ov, (size_t)2 * nprobes, h->stream);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(stage, d_ov, (size_t)2 * nprobes * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      }
+      const double s = lz.scale();  // q_k = s * X_k
+      double a, bt;
+      rc = lz.step(&a, &bt);
+      if (rc) return rc;
+      for (int j = 0; j < 2 * nprobes; ++j) ov[j] = stage[j] * s;
+      alanc[k] = a;
+      if (k + 1 < nlanc) blanc[k + 1] = bt;
+      if (std::fabs(bt) < threshold) {
+        ++k;
+        break;
+      }
+      if (k + 1 < nlanc) {
+        rc = lz.advance();
+        if (rc) return rc;
+      }
     }
   }
   HIPCHK(hipStreamSynchronize(h->stream));
-  *nsteps = k;
+  if (nsteps) *nsteps = k;
   return HXV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int hxv_lanczos_tridiag(hxv_handle* h, const void* d_vin, int32_t nlanc, double* alanc, double* blanc, double threshold,
+                        int32_t* nsteps) {
+  if (!h) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag: NULL handle");
+  const int rc_args = (!d_vin || nlanc < 1 || !alanc || !blanc) ? fail(HXV_ERR_ARG, "hxv_lanczos_tridiag: bad argument") : HXV_OK;
+  return tridiag_run(h, "hxv_lanczos_tridiag", rc_args, d_vin, 0, nullptr, nlanc, alanc, blanc, nullptr, threshold, nsteps);
+}
+
+// The tridiagonalisation with the overlaps <p_j|q_k> of every Lanczos vector (include/hxv.h): the off-diagonal Green's functions G_ij of one
+// orbital i from ONE run instead of the reference's mixed channels (ED_GF_NORMAL.f90:315-903).
+int hxv_lanczos_tridiag_probes(hxv_handle* h, const void* d_vin, int32_t nprobes, const void* const* d_probes, int32_t nlanc, double* alanc,
+                               double* blanc, double* overlaps, double threshold, int32_t* nsteps) {
+  if (!h) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: NULL handle");
+  auto check_args = [&]() -> int {
+    if (!d_vin || nlanc < 1 || !alanc || !blanc || !nsteps) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: bad argument (NULL start vector or output, or nlanc < 1)");
+    if (nprobes < 0 || nprobes > HXV_MAX_PROBES) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: nprobes must be 0 .. HXV_MAX_PROBES (8)");
+    if (nprobes > 0 && (!d_probes || !overlaps)) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: nprobes > 0 needs the probe list and the overlaps array");
+    for (int j = 0; j < nprobes; ++j) {
+      if (!d_probes[j]) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: NULL entry in the probe list");
+      // (ensure_lz clears the slab's place in the gather buffers; a START vector there is staged, a probe is the caller's to keep elsewhere)
+      if (comm_ready(h) && comm_in_gather(h, d_probes[j])) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: a probe lies in a gather buffer of the handle (hxv_slab_home): the driver clears that place");
+    }
+    return HXV_OK;
+  };
+  return tridiag_run(h, "hxv_lanczos_tridiag_probes", check_args(), d_vin, nprobes, d_probes, nlanc, alanc, blanc, overlaps, threshold, nsteps);
 }
 
 // Poles and weights of <p_j|(z - H)^{-1}|v> from one run of hxv_lanczos_tridiag_probes (include/hxv.h).  Host code only.
@@ -1086,18 +1033,8 @@ int hxv_lanczos_eigh(hxv_handle* h, int32_t nitermax, double threshold, double* 
   const int g = grid_for(n);
   const int nmax = (int)std::min<int64_t>(nitermax, h->host.dim);
   const uint64_t seed = 0x5EED5EEDull;
-  // deterministic start vector, normalised
-  auto start = [&](LzRunner& lz) -> int {
-    if (real)
-      launch_init_real(h, (double*)lz.b.w, seed, h->stream);
-    else
-      launch_init(h, lz.b.w, seed, h->stream);
-    HIPCHK(hipMemsetAsync(h->d_scalars, 0, 8 * sizeof(double), h->stream));
-    int rcn = enqueue_normalise(h, lz.b.q, lz.b.w, n, LZ_BETA);
-    return rcn ? rcn : lz.begin(1.0);
-  };
   LzRunner lz(h, h->lz_vec[0], h->lz_vec[1], h->lz_vec[2], real);
-  rc = start(lz);
+  rc = lz.begin_own(seed);
   if (rc) return rc;
   std::vector<double> al, be(1, 0.0);
   double e_old = 1e300, e_new = 0;
@@ -1149,7 +1086,7 @@ int hxv_lanczos_eigh(hxv_handle* h, int32_t nitermax, double threshold, double* 
     const double* y = &z[(size_t)jmin * m];
     double2* out = (double2*)d_vect;
     LzRunner lz2(h, h->lz_vec[0], h->lz_vec[1], h->lz_vec[2], real);
-    rc = start(lz2);
+    rc = lz2.begin_own(seed);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(out, 0, (size_t)n * sizeof(double2), h->stream));
     for (int j = 0; j < m; ++j) {
@@ -1187,31 +1124,26 @@ int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_v
   if (int rcc = need_comm(h, "device Lanczos")) return rcc;
   if (!h->lz_fused) return fail(HXV_ERR_UNSUPPORTED, "hxv_lanczos_tridiag_pair needs the fused recurrence (option lanczos_fused)");
   HIPCHK(hipSetDevice(h->device));
-  StageFree staged{h, {nullptr, nullptr}};
+  PoolGuard pooled{h, {}};
   const int64_t n = lz_len(h, false);
   const int g = grid_for(n);
   // scalars: the LzSlot block of component a, the one of b LZ_PAIR behind it (the handle's d_scalars has room for one only); the block
   // partials of the start vectors' check behind them
-  double* d_sc = nullptr;
+  DevFree sc_mem{h->stream};
   // every rank-local preparation that can fail comes BEFORE the agreement: a rank that cannot go on makes all ranks return
   auto prepare = [&]() -> int {
-    int r = stage_start_vector(h, d_vin_a, &staged.p[0]);  // (start vectors at hxv_slab_home: staged before their home is cleared)
-    if (!r) r = stage_start_vector(h, d_vin_b, &staged.p[1]);
+    int r = stage_start_vector(h, d_vin_a, pooled);  // (start vectors at hxv_slab_home: staged before their home is cleared)
+    if (!r) r = stage_start_vector(h, d_vin_b, pooled);
     if (!r) r = ensure_lz(h, false);  // (split sector: vectors are this rank's slab, every sum below is all-reduced)
     if (!r) r = ensure_wt(h);
     if (!r) r = ensure_lz_partial(h, 2 * lz_pass_a_workgroups(h, false));
     if (r) return r;
-    HIPCHK(hipMalloc((void**)&d_sc, (size_t)(2 * LZ_PAIR + 3 * RED_BLOCKS) * sizeof(double)));
+    HIPCHK(hipMalloc((void**)&sc_mem.p, (size_t)(2 * LZ_PAIR + 3 * RED_BLOCKS) * sizeof(double)));
     return HXV_OK;
   };
   int rc = comm_agree(h, prepare());
-  struct Free {
-    double*& p;
-    ~Free() {
-      if (p) (void)hipFree(p);
-    }
-  } guard{d_sc};
   if (rc) return rc;
+  double* const d_sc = sc_mem.p;
   double* d_p0 = d_sc + 2 * LZ_PAIR;
   double* d_p1 = d_p0 + RED_BLOCKS;
   double* d_p2 = d_p1 + RED_BLOCKS;
@@ -1231,7 +1163,7 @@ int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_v
   LzScale scale[2];
   bool alive[2] = {true, true};
   int done[2] = {0, 0};
-  for (int c = 0; c < 2; ++c) scale[c].begin(std::fabs(head[1 + c] - 1.0) <= 1e-14 ? 1.0 : head[1 + c]);
+  for (int c = 0; c < 2; ++c) scale[c].begin(start_norm(head[1 + c]));
   double* al[2] = {alanc_a, alanc_b};
   double* bl[2] = {blanc_a, blanc_b};
   bool first = true;
@@ -1321,187 +1253,6 @@ int hxv_lanczos_eigh_host(hxv_handle* h, int32_t nitermax, double threshold, dou
   return HXV_OK;
 }
 
-int hxv_apply_ladder(hxv_handle* from, hxv_handle* to, int32_t orbital, int32_t spin, int32_t create, const void* d_psi, void* d_out,
-                     double* norm2) {
-  return hxv_apply_ladder_axpy(from, to, orbital, spin, create, 1.0, 0.0, 0, d_psi, d_out, norm2);
-}
-
-namespace {
-// out[c][:] = (accumulate ? out[c][:] : 0) + coef * sign[c] * src_c[:]  for the local target columns c of a spin-dw ladder operator on a
-// split sector: src_c = column slot[c] of the local source slab (slot >= 0), column -1-slot[c] of the received columns (slot < 0),
-// or nothing (sign[c] == 0: the target column is not reached).  Rows are untouched by a dw operator; pad rows stay as they are.
-__global__ void __launch_bounds__(256) ladder_cols_kernel(int dimup, int ncols, int pitch_from, int pitch_to, const int32_t* __restrict__ slot,
-                                                         const int32_t* __restrict__ sign, const double2* __restrict__ psi_local,
-                                                         const double2* __restrict__ recv, double2* __restrict__ out, double2 coef, int accumulate) {
-  const int c = blockIdx.x;
-  if (c >= ncols) return;
-  const int sg = sign[c];
-  const double2* __restrict__ src = sg == 0 ? nullptr : (slot[c] >= 0 ? psi_local + (int64_t)slot[c] * pitch_from : recv + (int64_t)(-1 - slot[c]) * pitch_from);
-  double2* __restrict__ dst = out + (int64_t)c * pitch_to;
-  for (int i = threadIdx.x; i < dimup; i += 256) {
-    double2 r = make_double2(0.0, 0.0);
-    if (sg != 0) {
-      const double2 x = src[i];
-      r = make_double2(sg * (coef.x * x.x - coef.y * x.y), sg * (coef.x * x.y + coef.y * x.x));
-    }
-    if (accumulate) {
-      const double2 o = dst[i];
-      r.x += o.x;
-      r.y += o.y;
-    }
-    dst[i] = r;
-  }
-}
-
-// position of a bit pattern in a sorted sector map (ED_SETUP.f90:1044-1061 binary_search), -1 if absent
-int rank_in_map_host(const std::vector<uint32_t>& map, uint32_t m) {
-  auto it = std::lower_bound(map.begin(), map.end(), m);
-  return (it != map.end() && *it == m) ? (int)(it - map.begin()) : -1;
-}
-}  // namespace
-
-int hxv_apply_ladder_axpy(hxv_handle* from, hxv_handle* to, int32_t orbital, int32_t spin, int32_t create, double coef_re, double coef_im,
-                          int32_t accumulate, const void* d_psi, void* d_out, double* norm2) {
-  if (!from || !to || !d_psi || !d_out) return fail(HXV_ERR_ARG, "hxv_apply_ladder: NULL argument");
-  const SectorHost &a = from->host, &b = to->host;
-  if (a.map_up.empty() || b.map_up.empty()) return fail(HXV_ERR_STATE, "hxv_apply_ladder needs handles built from a model (basis maps)");
-  if (from->device != to->device) return fail(HXV_ERR_ARG, "hxv_apply_ladder: handles on different devices");
-  if (a.ns != b.ns || orbital < 0 || orbital >= a.ns || spin < 0 || spin > 1) return fail(HXV_ERR_ARG, "hxv_apply_ladder: bad orbital/spin");
-  const int d = create ? 1 : -1;
-  if (spin == 0 ? (b.nup != a.nup + d || b.ndw != a.ndw) : (b.ndw != a.ndw + d || b.nup != a.nup))
-    return fail(HXV_ERR_ARG, "hxv_apply_ladder: `to` is not the sector reached by this operator");
-  if (a.nranks != b.nranks || a.rank != b.rank) return fail(HXV_ERR_ARG, "hxv_apply_ladder: the two sectors must be split over the same ranks");
-  const bool split = b.nranks != 1 || comm_ready(to);
-  if (split && !comm_ready(to)) return fail(HXV_ERR_STATE, "hxv_apply_ladder on split sectors needs the communicator of `to` (hxv_comm_init after opening it)");
-  HIPCHK(hipSetDevice(to->device));
-  hipStream_t st = to->stream;
-  const double2 coef = make_double2(coef_re, coef_im);
-  // The reference applies c / c^dagger on the master and scatters the result (ED_GF_NORMAL.f90:174-214).  Here every rank builds its
-  // own slab of the new vector:
-  //  * spin up: the operator acts inside a column and both sectors have the same DimDw, hence the same split -- purely local;
-  //  * spin dw: target column j of sector B is (a sign times) ONE column of sector A, which may belong to another rank of A's split:
-  //    a column permutation.  Every rank derives from the two dw maps what it needs from whom and what everybody needs from it
-  //    (deterministic, no negotiation), packs, exchanges once, and assembles.
-  // a dw operator keeps the row: the two sectors -- same nup, same model -- must store their rows in the same order, split or not
-  if (spin == 1 && (a.row_order() != b.row_order() || (a.row_order() && a.up_pos != b.up_pos)))
-    return fail(HXV_ERR_STATE, "hxv_apply_ladder: the two sectors store their rows in different orders (HXV_ROW_ORDER changed between the opens?)");
-  if (!accumulate) HIPCHK(hipMemsetAsync(d_out, 0, (size_t)b.pitch * std::max(b.qdw, 1) * sizeof(double2), st));  // pad rows = 0
-  if (spin == 0 || !split) {
-    // spin up with a device row order (SectorHost::up_perm): the source row is looked up in the source sector's SORTED reference map and sent
-    // through its permutation; `to`'s map is by device row already; both basis signs ride along.  A dw operator keeps the row (same row
-    // order on both sides, checked above): nothing to do.
-    const uint32_t* mf = spin == 0 ? (a.row_order() ? from->dev.map_up_ref : from->dev.diag.map_up) : from->dev.diag.map_dw;
-    const uint32_t* mt = spin == 0 ? to->dev.diag.map_up : to->dev.diag.map_dw + b.dw0;  // (dw: the local target columns)
-    if (spin == 0 && a.qdw != b.qdw) return fail(HXV_ERR_STATE, "hxv_apply_ladder: the DimDw splits of the two sectors differ");
-    hipError_t e = launch_ladder(mf, spin == 0 ? a.dimup : a.dimdw, mt, spin == 0 ? b.dimup : b.dimdw, a.pitch, b.dimup, b.pitch, b.qdw,
-                                 orbital, spin, create ? 1 : 0, (const double2*)d_psi, (double2*)d_out, st, coef, accumulate ? 1 : 0,
-                                 spin == 0 ? from->dev.up_perm : nullptr, spin == 0 ? from->dev.up_sign : nullptr, spin == 0 ? to->dev.up_sign : nullptr);
-    if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string("ladder kernel: ") + hipGetErrorString(e));
-  } else {
-    const int P = b.nranks, r = b.rank;
-    const uint32_t bit = 1u << orbital;
-    // source column (global, in A) and sign of a target column (global, in B); -1: not reached
-    auto source_of = [&](int jb, int& sg) -> int {
-      const uint32_t mb = b.map_dw[jb];
-      if (((mb & bit) != 0u) != (create != 0)) return -1;
-      const uint32_t ma = mb ^ bit;
-      sg = (__builtin_popcount(ma & (bit - 1u)) & 1) ? -1 : 1;  // (-1)^(occupied orbitals of this spin below `orbital`): c/cdg, ED_SETUP.f90:807-833
-      return rank_in_map_host(a.map_dw, ma);
-    };
-    std::vector<int> first_a(P + 1), first_b(P + 1);
-    for (int p = 0; p < P; ++p) {
-      int q, c0;
-      dw_split(a.dimdw, p, P, q, c0);
-      first_a[p] = c0;
-      dw_split(b.dimdw, p, P, q, c0);
-      first_b[p] = c0;
-    }
-    first_a[P] = a.dimdw;
-    first_b[P] = b.dimdw;
-    auto owner_a = [&](int ja) { return (int)(std::upper_bound(first_a.begin(), first_a.end(), ja) - first_a.begin()) - 1; };
-    // what I receive: my target columns in order, grouped by the source's owner; what I send: every peer's target columns in ITS order
-    std::vector<int32_t> slot(std::max(b.qdw, 1), 0), sgn(std::max(b.qdw, 1), 0), send_cols;
-    std::vector<int64_t> recv_ptr(P + 1, 0), send_ptr(P + 1, 0);
-    std::vector<std::vector<int>> want(P);  // per owner: my local target columns whose source it holds, ascending
-    for (int c = 0; c < b.qdw; ++c) {
-      int sg = 0;
-      const int ja = source_of(b.dw0 + c, sg);
-      if (ja < 0) continue;
-      sgn[c] = sg;
-      const int o = owner_a(ja);
-      if (o == r)
-        slot[c] = ja - a.dw0;
-      else
-        want[o].push_back(c);
-    }
-    int nrecv = 0;
-    for (int p = 0; p < P; ++p) {
-      recv_ptr[p] = nrecv;
-      for (int c : want[p]) slot[c] = -1 - nrecv++;
-    }
-    recv_ptr[P] = nrecv;
-    for (int p = 0; p < P; ++p) {
-      send_ptr[p] = (int64_t)send_cols.size();
-      if (p == r) continue;
-      for (int jb = first_b[p]; jb < first_b[p + 1]; ++jb) {
-        int sg = 0;
-        const int ja = source_of(jb, sg);
-        if (ja >= 0 && owner_a(ja) == r) send_cols.push_back(ja - a.dw0);
-      }
-    }
-    send_ptr[P] = (int64_t)send_cols.size();
-    const size_t cb = (size_t)a.pitch * sizeof(double2);
-    double2 *d_sendbuf = nullptr, *d_recvbuf = nullptr;
-    int32_t* d_lists = nullptr;
-    const size_t nl = send_cols.size() + 2 * (size_t)std::max(b.qdw, 1);
-    int rc_local = HXV_OK;
-    hipError_t e1 = pool_alloc(to->device, std::max<size_t>(send_cols.size(), 1) * cb, (void**)&d_sendbuf);
-    hipError_t e2 = pool_alloc(to->device, std::max<size_t>((size_t)nrecv, 1) * cb, (void**)&d_recvbuf);
-    hipError_t e3 = hipMalloc((void**)&d_lists, std::max<size_t>(nl, 1) * sizeof(int32_t));
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) rc_local = fail(HXV_ERR_HIP, "hxv_apply_ladder: staging buffers for the column exchange");
-    auto release = [&]() {
-      (void)hipStreamSynchronize(st);
-      if (d_sendbuf) pool_free(to->device, d_sendbuf);
-      if (d_recvbuf) pool_free(to->device, d_recvbuf);
-      if (d_lists) (void)hipFree(d_lists);
-    };
-    int rc = comm_agree(to, rc_local);
-    if (rc) {
-      release();
-      return rc;
-    }
-    int32_t* d_send_cols = d_lists;
-    int32_t* d_slot = d_lists + send_cols.size();
-    int32_t* d_sgn = d_slot + std::max(b.qdw, 1);
-    hipError_t e = hipSuccess;
-    if (!send_cols.empty()) e = hipMemcpyAsync(d_send_cols, send_cols.data(), send_cols.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_slot, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_sgn, sgn.data(), sgn.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = launch_pack_columns((const double2*)d_psi, d_sendbuf, d_send_cols, (int)send_cols.size(), a.pitch, st);
-    if (e != hipSuccess) {
-      release();
-      return fail(HXV_ERR_HIP, std::string("hxv_apply_ladder: ") + hipGetErrorString(e));
-    }
-    rc = comm_sendrecv_cols(to, d_sendbuf, send_ptr.data(), d_recvbuf, recv_ptr.data(), cb, st);
-    if (rc) {
-      release();
-      return rc;
-    }
-    if (b.qdw > 0)
-      hipLaunchKernelGGL(ladder_cols_kernel, dim3((unsigned)b.qdw), dim3(256), 0, st, b.dimup, b.qdw, a.pitch, b.pitch, d_slot, d_sgn, (const double2*)d_psi,
-                         d_recvbuf, (double2*)d_out, coef, accumulate ? 1 : 0);
-    release();  // (synchronises the stream: the host lists above are read by asynchronous copies)
-  }
-  if (norm2) {
-    // <out|out> over ALL ranks of a split sector (pads of d_out must be zero: hxv.h)
-    int rcn = enqueue_norm(to, (const double2*)d_out, (int64_t)b.pitch * b.qdw, LZ_TMP, 0);
-    if (rcn) return rcn;
-    HIPCHK(hipMemcpyAsync(norm2, to->d_scalars + LZ_TMP, sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  return HXV_OK;
-}
-
 int hxv_time_lanczos(hxv_handle* h, void* d_work3, int32_t nrep, float* ms_per_iter) {
   if (!h || !d_work3 || nrep < 1 || !ms_per_iter) return fail(HXV_ERR_ARG, "hxv_time_lanczos: bad argument");
   if (h->host.nranks != 1) return fail(HXV_ERR_STATE, "hxv_time_lanczos needs nranks==1");
@@ -1511,34 +1262,16 @@ int hxv_time_lanczos(hxv_handle* h, void* d_work3, int32_t nrep, float* ms_per_i
   const bool real = want_real(h);
   LzRunner lz(h, (double2*)d_work3, (double2*)d_work3 + n, (double2*)d_work3 + 2 * n, real);
   n = lz.n2;
-  if (real)
-    launch_init_real(h, (double*)lz.b.w, 0x1234ull, h->stream);
-  else
-    launch_init(h, lz.b.w, 0x1234ull, h->stream);
-  HIPCHK(hipMemsetAsync(h->d_scalars, 0, 8 * sizeof(double), h->stream));
-  int rc = enqueue_normalise(h, lz.b.q, lz.b.w, n, LZ_BETA);
+  int rc = lz.begin_own(0x1234ull);
   if (rc) return rc;
   HIPCHK(hipMemsetAsync(lz.b.qm, 0, (size_t)n * sizeof(double2), h->stream));
-  rc = lz.begin(1.0);
-  if (rc) return rc;
   double a, bt;
   rc = lz.step(&a, &bt);  // untimed first step (lazy allocations)
   if (rc) return rc;
   if (lz.fused && h->lz_graph && nrep >= 8 && !comm_ready(h)) {
     // the fixed-length device-only path of hxv_lanczos_tridiag: iterations 1..nrep, three per hipGraph
-    double* d_ab = nullptr;
-    HIPCHK(hipMalloc((void**)&d_ab, (size_t)2 * (nrep + 1) * sizeof(double)));
-    hipError_t e = lz.begin_device_iterations(bt);
-    if (e == hipSuccess) e = hipEventRecord(h->ev0, h->stream);
-    rc = e != hipSuccess ? fail(HXV_ERR_HIP, std::string("hxv_time_lanczos: ") + hipGetErrorString(e))
-                         : lz.run_device_iterations(nrep + 1, d_ab, d_ab + nrep + 1, true);
-    if (rc == HXV_OK) {
-      e = hipEventRecord(h->ev1, h->stream);
-      if (e == hipSuccess) e = hipEventSynchronize(h->ev1);
-      if (e != hipSuccess) rc = fail(HXV_ERR_HIP, std::string("hxv_time_lanczos: ") + hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d_ab);
+    hipEvent_t ev[2] = {h->ev0, h->ev1};
+    rc = lz.run_device_only(bt, nrep + 1, nullptr, ev, "hxv_time_lanczos");
     if (rc) return rc;
     float msg = 0;
     HIPCHK(hipEventElapsedTime(&msg, h->ev0, h->ev1));

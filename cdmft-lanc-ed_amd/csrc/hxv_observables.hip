@@ -68,11 +68,6 @@ inline bool hop(uint32_t m, int is, int js, uint32_t& k, int& sg) {
   return true;
 }
 
-int rank_in(const std::vector<uint32_t>& map, uint32_t m) {
-  auto it = std::lower_bound(map.begin(), map.end(), m);
-  return (it != map.end() && *it == m) ? (int)(it - map.begin()) : -1;
-}
-
 std::string build_tables(const SectorHost& s, int nimp, int device, ObsTables& t) {
   const int nw = 1 << nimp, np = nimp * nimp;
   const uint32_t mask = (uint32_t)nw - 1u;
@@ -295,8 +290,6 @@ __global__ void __launch_bounds__(OBS_THREADS) obs_reduce_kernel(const double2* 
     }
   }
 }
-
-int nimp_of(const SectorHost& s) { return s.cross.nlat * s.cross.norb; }
 }  // namespace
 
 extern "C" {

@@ -22,7 +22,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "cdmft-lanc-ed_amd" / "csrc"
 HIPCC = "/opt/rocm/bin/hipcc"
-KERNEL_SOURCES = ["hxv_tiled.hip", "hxv_jobs.hip", "hxv_kernels.hip", "hxv_lanczos.hip", "hxv_eigh.hip"]
+KERNEL_SOURCES = ["hxv_tiled.hip", "hxv_jobs.hip", "hxv_kernels.hip", "hxv_lanczos.hip", "hxv_ladder.hip", "hxv_eigh.hip"]
 LANE_OPS = ("v_writelane", "v_readlane", "v_readfirstlane")
 
 

@@ -888,3 +888,90 @@ def test_impurity_green_function_free_fermion_closed_form(built, site, spin):
         sec.close()
     gs.close()
     assert np.abs(G - Gexact).max() <= 1e-9, np.abs(G - Gexact).max()
+
+
+# ---- the start-up of the tridiagonalisation drivers: start-vector norm, nsteps == NULL, the timer --------------------------------------
+def _start_norm_sector(name):
+    """-> (sector, unit start vector on the host): the chain has several columns and pad rows in both layouts and a real start vector; bhz
+    has a complex H and a complex start vector, so real mode cannot be chosen"""
+    import hxv
+    from hxv import models
+
+    rng = np.random.default_rng(17)
+    if name == "chain":
+        sec = hxv.HxvSector.from_model(models.hm_1dchain(Nlat=2, Nbath=2), 4, 3)
+        v = rng.standard_normal(sec.Dim).astype(np.complex128)
+    else:
+        sec = hxv.HxvSector.from_model(models.bhz_2d(Nbath=0, Ust=0.3, Jh=0.1), 4, 3)
+        v = rng.standard_normal(sec.Dim) + 1j * rng.standard_normal(sec.Dim)
+    return sec, v / np.linalg.norm(v)
+
+
+@pytest.mark.parametrize("fused", [0, 1])
+@pytest.mark.parametrize("graph", [0, 1])
+@pytest.mark.parametrize("real_vectors", [0, 1])
+def test_start_vector_norm_in_every_recurrence_variant(built, fused, graph, real_vectors):
+    """A start vector of norm 1 and the same vector at norm 2.5 through hxv_lanczos_tridiag and through the probes entry without probes, in
+    every combination of lanczos_fused, lanczos_graph and real_vectors: the three branches of the start-norm rule (norm 1: taken as it is;
+    fused: the recurrence carries the factor; plain: scaled in place).  The two entries give the same bits; the scaled run is the unit run
+    up to the roundings of one scaling: 1e-10 of the largest entry, the tolerance of test_fused_and_plain_recurrence_agree for two roundings
+    of the same recurrence."""
+    nl = 24
+    for name in ("chain", "bhz"):
+        sec, v = _start_norm_sector(name)
+        sec.set_option("lanczos_fused", fused)
+        sec.set_option("lanczos_graph", graph)
+        sec.set_option("real_vectors", real_vectors)
+        runs = []
+        for scale in (1.0, 2.5):
+            dv = sec.vector_from_host(scale * v)
+            a, b, n = sec.lanczos_tridiag(dv, nl)
+            assert sec.get_option("lanczos_real_last") == (1 if name == "chain" and real_vectors else 0)
+            ap, bp, _, n_p = sec.lanczos_tridiag_probes(dv, [], nl)
+            assert n == n_p == nl and np.array_equal(a, ap) and np.array_equal(b, bp), (name, scale)
+            runs.append((a, b))
+        (a1, b1), (a2, b2) = runs
+        print(f"{name} fused={fused} graph={graph} real_vectors={real_vectors}: max |d alanc| = {np.abs(a2 - a1).max():.3e} "
+              f"(max {np.abs(a1).max():.3e}), max |d blanc| = {np.abs(b2 - b1).max():.3e} (max {np.abs(b1).max():.3e})")
+        assert np.abs(a2 - a1).max() <= 1e-10 * np.abs(a1).max()
+        assert np.abs(b2 - b1).max() <= 1e-10 * np.abs(b1).max()
+        sec.close()
+
+
+def test_tridiag_accepts_a_null_nsteps(built):
+    """hxv_lanczos_tridiag called through ctypes with nsteps = NULL: returns 0 and fills the arrays exactly as the call with nsteps does."""
+    import ctypes as C
+    import torch
+    import hxv
+
+    sec, v = _start_norm_sector("chain")
+    dv = sec.vector_from_host(v)
+    L, pd, nl = hxv.load_library(), C.POINTER(C.c_double), 24
+    torch.cuda.synchronize()
+    out = []
+    for n in (C.c_int32(-1), None):
+        a, b = np.full(nl, 7.0), np.full(nl, 7.0)
+        rc = L.hxv_lanczos_tridiag(sec._h, dv.data_ptr(), nl, a.ctypes.data_as(pd), b.ctypes.data_as(pd), 1e-12, C.byref(n) if n is not None else None)
+        assert rc == 0, L.hxv_last_error()
+        out.append((a, b))
+        if n is not None:
+            assert n.value == nl
+    assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
+    assert np.abs(out[0][0]).max() > 0 and out[0][1][0] == 0.0
+    sec.close()
+
+
+@pytest.mark.parametrize("graph", [0, 1])
+def test_time_lanczos_leaves_the_handle_usable(built, graph):
+    """hxv_time_lanczos through its host loop (3 iterations) and its device-only path (9): a finite positive time each, and a
+    tridiagonalisation before and after them gives identical bits."""
+    sec, v = _start_norm_sector("chain")
+    sec.set_option("lanczos_graph", graph)
+    dv = sec.vector_from_host(v)
+    a0, b0, n0 = sec.lanczos_tridiag(dv, 24)
+    for nrep in (3, 9):
+        ms = sec.time_lanczos(nrep)
+        assert np.isfinite(ms) and ms > 0.0, (nrep, ms)
+    a1, b1, n1 = sec.lanczos_tridiag(dv, 24)
+    assert n0 == n1 == 24 and np.array_equal(a0, a1) and np.array_equal(b0, b1)
+    sec.close()
