@@ -132,6 +132,11 @@ struct SectorImage {
   struct CdmTables;
   std::shared_ptr<CdmTables> cdm;
   std::mutex cdm_mu;
+  // the group tables and work lists of the subset density matrices (hxv_reduced_dm.hip), one per (orbital mask, sign convention) asked for,
+  // most recently used last, a few at most; built by hxv_reduced_dm_accumulate
+  struct RdmTables;
+  std::vector<std::pair<uint64_t, std::shared_ptr<RdmTables>>> rdm;
+  std::mutex rdm_mu;
   ~SectorImage();
 };
 // the cache of closed sectors' images (hxv_cache.cpp); an empty key means "do not cache"

@@ -60,6 +60,7 @@ module ED_HAMILTONIAN_GPU_HXV
   !cluster reduced density matrix of device-resident states (ED_OBSERVABLES.f90 density_matrix_impurity, cluster_density_matrix)
   public :: gpu_cluster_dm_dev
   public :: gpu_get_cluster_dm
+  public :: gpu_reduced_dm_dev
 
   !> A vector that lives on the device, in the layout of the sector it was made for.  Opaque: pass it back to the gpu_* routines.
   type :: gpu_vector
@@ -363,6 +364,19 @@ module ED_HAMILTONIAN_GPU_HXV
        integer(c_int32_t),value :: accumulate
        real(c_double)           :: cdm(*)
      end function hxv_cluster_dm_accumulate
+     integer(c_int64_t) function hxv_reduced_dm_elems(h,orbital_mask) bind(C,name="hxv_reduced_dm_elems")
+       import :: c_int64_t, c_int32_t, c_ptr
+       type(c_ptr),value        :: h
+       integer(c_int32_t),value :: orbital_mask   !uint32_t: the same 32 bits
+     end function hxv_reduced_dm_elems
+     integer(c_int) function hxv_reduced_dm_accumulate(h,d_psi,orbital_mask,fermi_sign,weight,accumulate,rdm) bind(C,name="hxv_reduced_dm_accumulate")
+       import :: c_int, c_int32_t, c_ptr, c_double
+       type(c_ptr),value        :: h,d_psi
+       integer(c_int32_t),value :: orbital_mask,fermi_sign
+       real(c_double),value     :: weight
+       integer(c_int32_t),value :: accumulate
+       real(c_double)           :: rdm(*)
+     end function hxv_reduced_dm_accumulate
   end interface
 
   type(c_ptr),save :: handle = c_null_ptr   !one open sector at a time (ED_HAMILTONIAN_COMMON.f90:17-18)
@@ -1173,6 +1187,56 @@ contains
     call check(hxv_cluster_dm_accumulate(vect%sector,vect%d,real(peso,c_double),merge(1_c_int32_t,0_c_int32_t,accumulate),cdm_sum),&
          "gpu_cluster_dm_dev")
   end subroutine gpu_cluster_dm_dev
+
+  !> One state of state_list into rdm, the reduced density matrix of the impurity orbitals orbital_mask(ilat,jorb) names -- the mask
+  !! ed_get_reduced_density_matrix_single takes (ED_IO/get_reduced_dm.f90:68-212) -- computed from the device-resident vector instead of a
+  !! masked trace of cluster_density_matrix, so for any Nimp: rdm(4**Nred,4**Nred), 1 <= Nred <= 4, element (io,jo) with
+  !! io = (iREDup + 2**Nred*iREDdw) + 1 (:146).  vect and peso as gpu_cluster_dm_dev takes them.  accumulate=.false. overwrites rdm (the first
+  !! state), .true. adds peso * (this state's matrix) to it.  fermi_sign absent or .false.: the reference's numbers (its sign factor, :148, is
+  !! +1 on every pair that contributes: a plain partial trace); .true.: the matrix with the Jordan-Wigner sign of the subset, whose spectrum is
+  !! physical for any mask (include/hxv.h).  On a split sector every rank calls it with its slab and holds the global matrix.
+  subroutine gpu_reduced_dm_dev(vect,orbital_mask,peso,rdm,accumulate,fermi_sign)
+    type(gpu_vector),intent(in) :: vect
+    logical,intent(in)          :: orbital_mask(:,:)   !(Nlat,Norb)
+    real(8),intent(in)          :: peso
+    complex(8),intent(inout)    :: rdm(:,:)
+    logical,intent(in)          :: accumulate
+    logical,intent(in),optional :: fermi_sign
+    real(c_double),allocatable  :: buf(:)
+    integer(c_int32_t)          :: mask,fs
+    integer(c_int64_t)          :: n
+    integer                     :: ilat,jorb,i,j,m
+    if(.not.vec_alive(vect))stop "gpu_reduced_dm_dev ERROR: empty vector, or its sector was closed under it (gpu_keep_sector keeps it open)"
+    if(size(orbital_mask)>32)stop "gpu_reduced_dm_dev ERROR: orbital_mask has more than 32 entries"
+    mask=0
+    do ilat=1,size(orbital_mask,1)
+       do jorb=1,size(orbital_mask,2)
+          if(orbital_mask(ilat,jorb))mask=ibset(mask,jorb+(ilat-1)*size(orbital_mask,2)-1)
+       enddo
+    enddo
+    fs=0; if(present(fermi_sign))fs=merge(1_c_int32_t,0_c_int32_t,fermi_sign)
+    n=hxv_reduced_dm_elems(vect%sector,mask)
+    if(n<=0)stop "gpu_reduced_dm_dev ERROR: no reduced density matrix for this mask on the open sector (1 to 4 orbitals inside Nimp; basis maps)"
+    m=size(rdm,1)
+    if(size(rdm,2)/=m.or.2_c_int64_t*int(m,c_int64_t)*m/=n)stop "gpu_reduced_dm_dev ERROR: rdm is not (4**Nred,4**Nred)"
+    allocate(buf(n))
+    if(accumulate)then
+       do j=1,m
+          do i=1,m
+             buf(2*(i+m*(j-1))-1)=dble(rdm(i,j))
+             buf(2*(i+m*(j-1)))=aimag(rdm(i,j))
+          enddo
+       enddo
+    endif
+    call check(hxv_reduced_dm_accumulate(vect%sector,vect%d,mask,fs,real(peso,c_double),merge(1_c_int32_t,0_c_int32_t,accumulate),buf),&
+         "gpu_reduced_dm_dev")
+    do j=1,m
+       do i=1,m
+          rdm(i,j)=cmplx(buf(2*(i+m*(j-1))-1),buf(2*(i+m*(j-1))),kind=8)
+       enddo
+    enddo
+    deallocate(buf)
+  end subroutine gpu_reduced_dm_dev
 
   !> The summed matrix into the reference's cluster_density_matrix(4**Nimp,4**Nimp) (ED_VARS_GLOBAL.f90), as is: element (io,jo),
   !! io = (IimpUp + 2**Nimp*IimpDw) + 1 (ED_OBSERVABLES.f90:561-566).

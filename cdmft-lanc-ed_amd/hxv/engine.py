@@ -49,7 +49,7 @@ EXPORTS = [
     "hxv_vector_alloc", "hxv_vector_alloc_many", "hxv_vector_free", "hxv_vector_from_host", "hxv_vector_to_host",
     "hxv_sector_cache_clear", "hxv_sector_cache_stats", "hxv_comm_abort", "hxv_comm_library", "hxv_comm_cache_stats", "hxv_comm_cache_clear", "hxv_host_register", "hxv_host_unregister",
     "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
-    "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_twin_vector", "hxv_twin_split_plan",
+    "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_reduced_dm_elems", "hxv_reduced_dm_accumulate", "hxv_twin_vector", "hxv_twin_split_plan",
     "hxv_lanczos_tridiag_probes", "hxv_gf_from_probes",
 ]
 
@@ -164,6 +164,9 @@ def load_library():
     L.hxv_cluster_dm_elems.argtypes = [vp]
     L.hxv_cluster_dm_elems.restype = i64
     L.hxv_cluster_dm_accumulate.argtypes = [vp, vp, dbl, i32, pd]
+    L.hxv_reduced_dm_elems.argtypes = [vp, C.c_uint32]
+    L.hxv_reduced_dm_elems.restype = i64
+    L.hxv_reduced_dm_accumulate.argtypes = [vp, vp, C.c_uint32, i32, dbl, i32, pd]
     L.hxv_twin_vector.argtypes = [vp, vp, vp, vp]
     L.hxv_twin_split_plan.argtypes = [i32, i32, i32, i32, pi64, pi64]
     L.hxv_lanczos_tridiag_probes.argtypes = [vp, vp, i32, C.POINTER(vp), i32, pd, pd, pd, dbl, pi32]
@@ -949,6 +952,47 @@ class HxvSector:
         torch.cuda.synchronize(psi_device.device)
         _chk(L.hxv_cluster_dm_accumulate(self._h, psi_device.data_ptr(), float(weight), int(bool(accumulate)),
                                          C.cast(out.ctypes.data, C.POINTER(C.c_double))), "hxv_cluster_dm_accumulate")
+        return out
+
+    @staticmethod
+    def _orbital_mask(orbitals) -> int:
+        """The bit mask hxv_reduced_dm_accumulate takes: `orbitals` is an iterable of impurity bit indices (b = iorb + ilat*Norb, 0-based)
+        or a bool array (Nlat, Norb), the reference's orbital_mask."""
+        a = np.asarray(orbitals if isinstance(orbitals, np.ndarray) else list(orbitals))
+        if a.dtype == np.bool_:
+            bits = np.flatnonzero(a.reshape(-1))   # C order of (Nlat, Norb): ilat*Norb + iorb
+        else:
+            bits = a.astype(np.int64).reshape(-1)
+            if bits.size != np.unique(bits).size:
+                raise HxvError("reduced_dm: an orbital is named twice")
+        if bits.size and (bits.min() < 0 or bits.max() > 31):
+            raise HxvError("reduced_dm: orbital bit outside 0..31")
+        return int(sum(1 << int(b) for b in bits))
+
+    def reduced_dm(self, psi_device, orbitals, weight: float = 1.0, fermi_sign: bool = False, out: np.ndarray | None = None,
+                   accumulate: bool = False) -> np.ndarray:
+        """Reduced density matrix of the impurity orbitals `orbitals` (bit indices or a bool array (Nlat, Norb); 1 to 4 of them, any Nimp) of one device-resident
+        state (include/hxv.h, hxv_reduced_dm_accumulate; the reference's ed_get_reduced_density_matrix_single, ED_IO/get_reduced_dm.f90),
+        weighted by `weight`: complex128 of shape (4^Nred, 4^Nred), element [io, jo] with io = a_up + 2^Nred a_dw, a the occupations of the
+        chosen orbitals in ascending orbital order.  fermi_sign=False is the reference's plain partial trace; fermi_sign=True carries the
+        Jordan-Wigner sign that makes the spectrum physical for any subset.  psi_device, out and accumulate as cluster_dm."""
+        import torch
+
+        assert psi_device.is_cuda and psi_device.dtype == torch.complex128 and psi_device.is_contiguous() and psi_device.numel() == self.localElems, \
+            "reduced_dm takes a device vector in the padded layout (localElems elements)"
+        L = load_library()
+        mask = self._orbital_mask(orbitals)
+        n = L.hxv_reduced_dm_elems(self._h, mask)
+        if n <= 0:   # a mask or a handle the library does not take: the call below writes nothing and reports which rule is broken
+            out = np.zeros((1, 1), dtype=np.complex128, order="F")
+        side = int(round((max(n, 2) // 2) ** 0.5))
+        if out is None:
+            assert not accumulate, "accumulate=True needs `out`"
+            out = np.zeros((side, side), dtype=np.complex128, order="F")
+        assert out.dtype == np.complex128 and out.flags.f_contiguous and out.shape == (side, side)
+        torch.cuda.synchronize(psi_device.device)
+        _chk(L.hxv_reduced_dm_accumulate(self._h, psi_device.data_ptr(), mask, int(bool(fermi_sign)), float(weight), int(bool(accumulate)),
+                                         C.cast(out.ctypes.data, C.POINTER(C.c_double))), "hxv_reduced_dm_accumulate")
         return out
 
     def time_lanczos(self, nrep: int) -> float:

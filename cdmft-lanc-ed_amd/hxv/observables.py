@@ -88,3 +88,15 @@ def cluster_density_matrix(model, states, beta: float | None = None) -> np.ndarr
     for (sec, _, psi), wi in zip(states, w):
         sec.cluster_dm(psi, weight=wi, out=rho, accumulate=True)
     return rho
+
+
+def reduced_density_matrix(model, states, orbital_mask, beta: float | None = None, fermi_sign: bool = False) -> np.ndarray:
+    """The reference's ed_get_reduced_density_matrix_single (ED_IO/get_reduced_dm.f90:68-212) of the whole state list without the dense
+    cluster matrix, so for any Nimp: rho_S = sum_i peso_i Tr_env |psi_i><psi_i|, S the impurity orbitals of `orbital_mask` (bit indices or a
+    bool array (Nlat, Norb)), complex (4^Nred, 4^Nred).  fermi_sign=False gives the reference's numbers (a plain partial trace), True the
+    matrix with the Jordan-Wigner sign; states and beta as in cluster_density_matrix()."""
+    w = thermal_weights([e for _, e, _ in states], beta)
+    rho = None
+    for (sec, _, psi), wi in zip(states, w):
+        rho = sec.reduced_dm(psi, orbital_mask, weight=wi, fermi_sign=fermi_sign, out=rho, accumulate=rho is not None)
+    return rho

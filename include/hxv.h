@@ -514,6 +514,34 @@ int hxv_observables_derive(const hxv_model *model, const double *record, double 
 int64_t hxv_cluster_dm_elems(const hxv_handle *h);
 int hxv_cluster_dm_accumulate(hxv_handle *h, const void *d_psi, double weight, int32_t accumulate, double *cdm /* host */);
 
+/* ---- reduced density matrix of a subset of the impurity orbitals, of device-resident states -----------------------------------
+ * ED_IO/get_reduced_dm.f90 ed_get_reduced_density_matrix_single (:68-212): rho_S = Tr_env |psi><psi|, S the Nred impurity orbitals named by
+ * orbital_mask, env everything else (the bath and the traced impurity orbitals).  The reference traces the dense cluster_density_matrix;
+ * this entry works from the vector, so there is no limit on Nimp (the cluster matrix above ends at Nimp 5):
+ *   rdm(io,jo) += weight * sum over (e_up,e_dw) of sg(i) sg(j) psi(a_up|e_up, a_dw|e_dw) * conj(psi(a'_up|e_up, a'_dw|e_dw)),
+ *   io = a_up + 2^Nred a_dw, jo = a'_up + 2^Nred a'_dw  (0-based), a = the occupations of the masked orbitals in ascending orbital order
+ *   (the reference's bjoin of state(red_indices), :193-210 and :146-147).
+ * orbital_mask: bit b is set when the impurity orbital whose bit in a spin configuration is b belongs to S; the reference's
+ *   b = jorb + (ilat-1)*Norb - 1 of orbital_mask(ilat,jorb) (:115), the low Nimp bits the cluster matrix indexes.  1 <= Nred <= 4.
+ * fermi_sign 0: sg = +1, the plain partial trace.  These are the reference's numbers: its get_sign (:170-191) zeroes the reduced orbitals
+ *   before it counts, the loop keeps pairs with equal traced bits (:145), so IsignUP*IsignDW*JsignUP*JsignDW (:148) is +1 for every pair that
+ *   contributes.  The spectrum of this matrix is physical for some subsets only: on Slater determinants of a four-orbital cluster the
+ *   entropy of S = {0,1} and {1,2,3} equals the closed form, that of S = {0,2} and {0,3} misses it by 2e-2 to 2.6e-1.
+ * fermi_sign 1: sg(i) = (-1)^n, n = for every occupied orbital r of S the number of occupied orbitals outside S below r, per spin: the
+ *   Jordan-Wigner string.  This matrix is the one whose spectrum (entanglement entropy, purity) is physical for any subset.
+ * hxv_reduced_dm_elems: the length of rdm in doubles, 2 * 16^Nred: complex(8), interleaved, Fortran order, element (io,jo) at
+ * 2*(io + 4^Nred*jo); Hermitian, the lower triangle filled by conjugation, the diagonal's imaginary part exactly 0.  0 for handles without
+ * basis maps, dw panels, an empty mask, a mask outside the Nimp bits and Nred > 4.
+ * hxv_reduced_dm_accumulate: d_psi, weight, accumulate, the stream, determinism (no floating-point atomics) and split sectors (collective,
+ * every rank returns the GLOBAL matrix, all ranks fail together) as hxv_cluster_dm_accumulate; weight * raw is rounded before the add, so
+ * an accumulated matrix equals the sum of the single results bit for bit.  The group tables of a (mask, fermi_sign) are built on first use
+ * and kept with the sector image, the last few of them.  Errors: HXV_ERR_ARG for NULL arguments, an empty mask, a mask outside the
+ * impurity bits and fermi_sign not 0 or 1; HXV_ERR_UNSUPPORTED for Nred > 4; HXV_ERR_STATE for a handle without basis maps (from CSR, a dw
+ * panel) and for a split sector without its communicator.                                                                           */
+int64_t hxv_reduced_dm_elems(const hxv_handle *h, uint32_t orbital_mask);
+int hxv_reduced_dm_accumulate(hxv_handle *h, const void *d_psi, uint32_t orbital_mask, int32_t fermi_sign, double weight, int32_t accumulate,
+                              double *rdm /* host */);
+
 /* ---- device vectors owned by the library --------------------------------------------------------------------------------
  * For host programs without a HIP binding of their own (the Fortran glue): a local vector of the handle's sector in the padded device
  * layout (hxv_localvec_elems() complex elements, zeroed), from the engine's buffer cache.  Such a pointer is what the device drivers take
