@@ -137,6 +137,10 @@ struct SectorImage {
   struct RdmTables;
   std::vector<std::pair<uint64_t, std::shared_ptr<RdmTables>>> rdm;
   std::mutex rdm_mu;
+  // the impurity-occupation words of the density-type operators (hxv_density_ops.hip), built on the first hxv_apply_density_ops
+  struct DopTables;
+  std::shared_ptr<DopTables> dop;
+  std::mutex dop_mu;
   ~SectorImage();
 };
 // the cache of closed sectors' images (hxv_cache.cpp); an empty key means "do not cache"

@@ -42,6 +42,7 @@ module ED_HAMILTONIAN_GPU_HXV
   !off-diagonal Green's functions from one run per orbital (include/hxv.h: hxv_lanczos_tridiag_probes, hxv_gf_from_probes)
   public :: gpu_sp_lanc_tridiag_probes_dev
   public :: gpu_gf_from_probes
+  public :: gpu_apply_density_ops_dev
   public :: gpu_vector_to_host
   public :: gpu_vector_from_host
   public :: gpu_free_vector
@@ -377,6 +378,14 @@ module ED_HAMILTONIAN_GPU_HXV
        integer(c_int32_t),value :: accumulate
        real(c_double)           :: rdm(*)
      end function hxv_reduced_dm_accumulate
+     integer(c_int) function hxv_apply_density_ops(h,nops,coef,subtract_mean,d_psi,d_out,mean,norm2) bind(C,name="hxv_apply_density_ops")
+       import :: c_int, c_int32_t, c_ptr, c_double
+       type(c_ptr),value         :: h,d_psi
+       integer(c_int32_t),value  :: nops,subtract_mean
+       real(c_double),intent(in) :: coef(*)
+       type(c_ptr),intent(in)    :: d_out(*)
+       real(c_double)            :: mean(*),norm2(*)
+     end function hxv_apply_density_ops
   end interface
 
   type(c_ptr),save :: handle = c_null_ptr   !one open sector at a time (ED_HAMILTONIAN_COMMON.f90:17-18)
@@ -907,6 +916,46 @@ contains
     call check(hxv_gf_from_probes(int(n,c_int32_t),a,b,int(np,c_int32_t),ov,norm,poles,w),"gpu_gf_from_probes")
     if(np>0)weights=w
   end subroutine gpu_gf_from_probes
+
+  !> Density-type operators on a device vector of the OPEN sector (include/hxv.h, hxv_apply_density_ops): the start vectors of the two-particle
+  !! stage (buildChi_impurity, ED_GREENS_FUNCTIONS.f90:68-106).  coef(is,1,a) / coef(is,2,a) are the coefficients of n_{is,up} / n_{is,dw}
+  !! in operator a, is = iorb+(ilat-1)*Norb over the Nimp impurity orbitals (S^z_i: +1/2, -1/2 on is = i; n_i: 1, 1);
+  !!     out(a) = (O_a - m_a) psi,   mean(a) = <psi|O_a|psi>/<psi|psi>,   m_a = mean(a) unless subtract_mean=.false.,   norm2(a) = <out(a)|out(a)>.
+  !! Empty entries of out are allocated on the open sector.  chi_ab then takes one gpu_sp_lanc_tridiag_probes_dev run per b from out(b) with
+  !! all out(:) as probes and gpu_gf_from_probes with norm = sqrt(norm2(b)):
+  !!     chi_ab(z) = - sum_n [ weights(a,n)/(z - de_n) - conjg(weights(a,n))/(z + de_n) ],   de_n = poles(n) - E,   poles with |de_n| <= 1d-8 left out
+  !! (the rounding ghosts of psi itself).  On a split sector psi and out are this rank's slabs and the call is collective.
+  subroutine gpu_apply_density_ops_dev(psi,coef,out,mean,norm2,subtract_mean)
+    type(gpu_vector),intent(in)    :: psi
+    real(8),intent(in)             :: coef(:,:,:)
+    type(gpu_vector),intent(inout) :: out(:)
+    real(8),intent(inout)          :: mean(:),norm2(:)
+    logical,intent(in),optional    :: subtract_mean
+    real(8),allocatable            :: cf(:,:,:)
+    real(8)                        :: m(8),n2(8)
+    type(c_ptr)                    :: olist(8)
+    integer(c_int32_t)             :: sub
+    integer                        :: a,nops
+    if(.not.c_associated(handle))stop "gpu_apply_density_ops_dev ERROR: Hsector NOT set"
+    if(psi%sector_id/=handle_serial.or..not.c_associated(psi%d))stop "gpu_apply_density_ops_dev ERROR: the state does not belong to the open sector"
+    nops=size(coef,3)
+    if(nops<1.or.nops>8)stop "gpu_apply_density_ops_dev ERROR: 1 to 8 operators"
+    if(size(coef,2)/=2.or.size(out)/=nops.or.size(mean)/=nops.or.size(norm2)/=nops)&
+         stop "gpu_apply_density_ops_dev ERROR: coef is (Nimp,2,nops); out, mean, norm2 have nops entries"
+    olist=c_null_ptr
+    do a=1,nops
+       if(.not.c_associated(out(a)%d))then
+          call check(hxv_vector_alloc(handle,out(a)%d),"gpu_apply_density_ops_dev")
+          call vec_born(out(a),out(a)%d,.false.)
+       endif
+       if(out(a)%sector_id/=handle_serial)stop "gpu_apply_density_ops_dev ERROR: an output does not belong to the open sector"
+       olist(a)=out(a)%d
+    enddo
+    sub=1; if(present(subtract_mean))then; if(.not.subtract_mean)sub=0; endif
+    allocate(cf(size(coef,1),2,nops)); cf=coef          !(contiguous, whatever section the caller passed)
+    call check(hxv_apply_density_ops(handle,int(nops,c_int32_t),cf,sub,psi%d,olist,m,n2),"gpu_apply_density_ops_dev")
+    mean=m(1:nops); norm2=n2(1:nops)
+  end subroutine gpu_apply_density_ops_dev
 
   !> the vector in the reference's host layout (this rank's slab), when it is wanted there after all (e.g. state_list of ED_DIAG)
   subroutine gpu_vector_to_host(vect,v)

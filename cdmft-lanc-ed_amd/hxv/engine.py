@@ -50,7 +50,7 @@ EXPORTS = [
     "hxv_sector_cache_clear", "hxv_sector_cache_stats", "hxv_comm_abort", "hxv_comm_library", "hxv_comm_cache_stats", "hxv_comm_cache_clear", "hxv_host_register", "hxv_host_unregister",
     "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
     "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_reduced_dm_elems", "hxv_reduced_dm_accumulate", "hxv_twin_vector", "hxv_twin_split_plan",
-    "hxv_lanczos_tridiag_probes", "hxv_gf_from_probes",
+    "hxv_lanczos_tridiag_probes", "hxv_gf_from_probes", "hxv_apply_density_ops",
 ]
 
 _lib = None
@@ -171,6 +171,7 @@ def load_library():
     L.hxv_twin_split_plan.argtypes = [i32, i32, i32, i32, pi64, pi64]
     L.hxv_lanczos_tridiag_probes.argtypes = [vp, vp, i32, C.POINTER(vp), i32, pd, pd, pd, dbl, pi32]
     L.hxv_gf_from_probes.argtypes = [i32, pd, pd, i32, pd, dbl, pd, pd]
+    L.hxv_apply_density_ops.argtypes = [vp, i32, pd, i32, vp, C.POINTER(vp), pd, pd]
     _lib = L
     return L
 
@@ -994,6 +995,43 @@ class HxvSector:
         _chk(L.hxv_reduced_dm_accumulate(self._h, psi_device.data_ptr(), mask, int(bool(fermi_sign)), float(weight), int(bool(accumulate)),
                                          C.cast(out.ctypes.data, C.POINTER(C.c_double))), "hxv_reduced_dm_accumulate")
         return out
+
+    def nimp(self) -> int:
+        """Nimp = Nlat * Norb of a sector built from a model, from the length 4^Nimp + 4 Nimp^2 of its observables record; 0 for a handle
+        without basis maps and for Nimp > 10."""
+        n = load_library().hxv_obs_record_elems(self._h)
+        return next((k for k in range(1, 11) if 4 ** k + 4 * k * k == n), 0)
+
+    def apply_density_ops(self, coef, psi, subtract_mean: bool = True, out=None):
+        """hxv_apply_density_ops (include/hxv.h): out_a = (O_a - m_a) psi for the density-type operators O_a = sum_is (cu_a[is] n_is,up +
+        cd_a[is] n_is,dw) over the Nimp impurity orbitals, m_a = <O_a> when subtract_mean, else 0: the start vectors and probes of the spin /
+        charge susceptibilities (hxv.observables.susceptibility).  coef: array (nops, 2, Nimp), cu then cd per operator, 1 <= nops <= 8.
+        psi: a device vector of this sector in the padded layout (localElems complex128 elements: this rank's slab on a split sector,
+        collective there).  out: a list of nops such vectors to write into, allocated when not given; every element is written.
+        -> (list of nops device vectors, mean[nops], norm2[nops])."""
+        import torch
+
+        if not (torch.is_tensor(psi) and psi.is_cuda and psi.dtype == torch.complex128 and psi.is_contiguous() and psi.numel() == self.localElems):
+            raise HxvError(f"apply_density_ops takes a device vector in the padded layout (complex128, localElems = {self.localElems} elements)")
+        cf = np.ascontiguousarray(coef, dtype=np.float64)
+        if cf.ndim != 3 or cf.shape[1] != 2 or cf.shape[0] < 1:
+            raise HxvError("apply_density_ops: coef has the shape (nops, 2, Nimp)")
+        nops = int(cf.shape[0])
+        nimp = self.nimp()
+        if nimp and cf.shape[2] != nimp:       # (a handle without basis maps or with Nimp > 10 is refused by the library before it reads coef)
+            raise HxvError(f"apply_density_ops: coef has the shape (nops, 2, Nimp = {nimp})")
+        if out is None:
+            out = [torch.empty(self.localElems, dtype=torch.complex128, device=psi.device) for _ in range(min(nops, 8))]
+        out = list(out)
+        for v in out:
+            if v is not None and not (torch.is_tensor(v) and v.is_cuda and v.dtype == torch.complex128 and v.is_contiguous() and v.numel() == self.localElems):
+                raise HxvError("apply_density_ops: every output is a device vector in the padded layout")
+        mean, norm2 = np.zeros(max(nops, 1)), np.zeros(max(nops, 1))
+        olist = (C.c_void_p * max(len(out), nops, 1))(*[None if v is None else v.data_ptr() for v in out])
+        torch.cuda.synchronize(psi.device)
+        _chk(load_library().hxv_apply_density_ops(self._h, nops, _p(cf, C.c_double), int(bool(subtract_mean)), psi.data_ptr(), olist,
+                                                  _p(mean, C.c_double), _p(norm2, C.c_double)), "hxv_apply_density_ops")
+        return out, mean[:nops], norm2[:nops]
 
     def time_lanczos(self, nrep: int) -> float:
         import torch

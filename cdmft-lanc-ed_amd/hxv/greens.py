@@ -40,3 +40,25 @@ def evaluate(poles, weights, z, e0: float, sign: float):
     z = np.asarray(z, dtype=np.complex128)
     den = 1.0 / (z[..., None] - sign * (poles - e0))          # z.shape + (n,)
     return np.tensordot(den, w, axes=([-1], [0]))
+
+
+def chi_evaluate(poles, weights, z, e_state: float, cutoff: float = 1e-8):
+    """The bosonic pole sum of a susceptibility column (include/hxv.h, hxv_apply_density_ops):
+
+        chi[..., a](z) = - sum_n [ w_n[a] / (z - e_n) - conj(w_n[a]) / (z + e_n) ],   e_n = poles[n] - e_state,
+
+    poles, weights from poles_weights() of the run started from dO_b|psi> with the probes dO_a|psi> and norm = |dO_b psi|; e_state the
+    energy of psi.  At z = i nu and real symmetric weights this is the reference's Lehmann form sum_n W_n 2 e_n / (nu^2 + e_n^2).
+    Poles with |e_n| <= cutoff are DROPPED: a run started from dO|psi> still finds psi itself (dO projects it out to rounding only), as
+    Ritz values within 1e-8 of e_state with weights of 1e-25, and at z = 0 such a pole is tiny / tiny, or x / 0.  A degenerate level that
+    carries real weight is the caller's Curie term, not this sum's.
+    -> (chi of shape z.shape + weights.shape[1:], dropped_weight = the summed |weight| of the dropped poles: assert it is negligible)."""
+    poles = np.asarray(poles, dtype=np.float64)
+    w = np.asarray(weights, dtype=np.complex128)
+    z = np.asarray(z, dtype=np.complex128)
+    e = poles - float(e_state)
+    keep = np.abs(e) > float(cutoff)
+    dropped = float(np.abs(w[~keep]).sum())
+    e, w = e[keep], w[keep]
+    chi = -(np.tensordot(1.0 / (z[..., None] - e), w, axes=([-1], [0])) - np.tensordot(1.0 / (z[..., None] + e), w.conj(), axes=([-1], [0])))
+    return chi, dropped

@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from .engine import HxvSector, _chk, _p, load_library
+from .engine import HxvError, HxvSector, _chk, _p, load_library
 
 # derive(): name, shape (Fortran order), dtype -- in the order of hxv_observables_derive's output
 _FIELDS = ["dens", "dens_up", "dens_dw", "docc", "magz", "sz2", "n2", "s2tot", "Eknot", "Epot", "Ehartree", "Dust", "Dund",
@@ -100,3 +100,49 @@ def reduced_density_matrix(model, states, orbital_mask, beta: float | None = Non
     for (sec, _, psi), wi in zip(states, w):
         rho = sec.reduced_dm(psi, orbital_mask, weight=wi, fermi_sign=fermi_sign, out=rho, accumulate=rho is not None)
     return rho
+
+
+def density_coefficients(kind, nimp: int) -> np.ndarray:
+    """coef (nops, 2, Nimp) of HxvSector.apply_density_ops: "spin" = S^z of every impurity orbital (cu = +1/2, cd = -1/2 on orbital a),
+    "charge" = n of every impurity orbital (cu = cd = 1); an array is taken as it is."""
+    if isinstance(kind, str):
+        if kind not in ("spin", "charge"):
+            raise HxvError('susceptibility: kind is "spin", "charge" or a coefficient array (nops, 2, Nimp)')
+        cf = np.zeros((nimp, 2, nimp))
+        for a in range(nimp):
+            cf[a, 0, a], cf[a, 1, a] = (0.5, -0.5) if kind == "spin" else (1.0, 1.0)
+        return cf
+    cf = np.ascontiguousarray(kind, dtype=np.float64)
+    if cf.ndim != 3 or cf.shape[1] != 2 or cf.shape[2] != nimp:
+        raise HxvError(f"susceptibility: a coefficient array has the shape (nops, 2, Nimp = {nimp})")
+    return cf
+
+
+def susceptibility(sec, psi, e_state: float, kind, z, nlanc: int = 200, cutoff: float = 1e-8):
+    """chi_ab(z) = <<dO_a; dO_b>> of ONE device-resident eigenstate psi (energy e_state) of the open sector `sec`: the impurity spin
+    ("spin": O_a = S^z_a) or charge ("charge": O_a = n_a) susceptibility between the impurity orbitals, or between the operators of an
+    explicit coefficient array (nops, 2, Nimp); the reference's buildChi_impurity stage (ED_GREENS_FUNCTIONS.f90:68-106).  One
+    apply_density_ops call builds every dO_a|psi>; column b is one lanczos_tridiag_probes run from dO_b|psi> with all dO_a|psi> as probes
+    (a column whose start vector has norm2 < 1e-24 is zero and is skipped), then greens.poles_weights and greens.chi_evaluate.  Nothing
+    Dim-sized crosses PCIe.  A thermal average is the caller's sum over the state list, sum_m peso_m chi^(m) (thermal_weights).
+    -> (chi[len(z), nops, nops] complex128, info = {"mean", "norm2", "nsteps", "dropped_weight"})."""
+    from . import greens
+
+    if not sec.nimp():
+        raise HxvError("susceptibility needs a sector built from a model with Nimp <= 10")
+    cf = density_coefficients(kind, sec.nimp())
+    nops = cf.shape[0]
+    if nops > 8:
+        raise HxvError("susceptibility: at most 8 operators per call (HXV_MAX_DENSITY_OPS, HXV_MAX_PROBES)")
+    z = np.asarray(z, dtype=np.complex128).reshape(-1)
+    vecs, mean, norm2 = sec.apply_density_ops(cf, psi, subtract_mean=True)
+    chi = np.zeros((z.size, nops, nops), dtype=np.complex128)
+    nsteps, dropped = np.zeros(nops, dtype=np.int64), 0.0
+    for b in range(nops):
+        if norm2[b] < 1e-24:
+            continue
+        al, bl, ov, n = sec.lanczos_tridiag_probes(vecs[b], vecs, min(int(nlanc), sec.Dim))
+        poles, wts = greens.poles_weights(al[:n], bl[:n], ov, np.sqrt(norm2[b]))
+        chi[:, :, b], d = greens.chi_evaluate(poles, wts, z, e_state, cutoff)
+        nsteps[b], dropped = n, dropped + d
+    return chi, dict(mean=mean, norm2=norm2, nsteps=nsteps, dropped_weight=dropped)

@@ -542,6 +542,38 @@ int64_t hxv_reduced_dm_elems(const hxv_handle *h, uint32_t orbital_mask);
 int hxv_reduced_dm_accumulate(hxv_handle *h, const void *d_psi, uint32_t orbital_mask, int32_t fermi_sign, double weight, int32_t accumulate,
                               double *rdm /* host */);
 
+/* ---- density-type operators on device-resident states: the start vectors of the spin and charge susceptibilities ---------------
+ * The two-particle stage of the reference (buildChi_impurity, ED_GREENS_FUNCTIONS.f90:68-106: spinChi, densChi) starts from O|psi> with
+ * O diagonal in the Fock basis.  For nops operators  O_a = sum_is (cu_a[is] n_is,up + cd_a[is] n_is,dw)  over the Nimp impurity orbitals
+ * (is = iorb + ilat*Norb, 0-based: the low Nimp bits of each spin's configuration, as in hxv_observables_accumulate) this entry computes
+ *     out_a = (f_a - m_a) psi  element by element,   f_a(iup,idw) = sum_is cu_a[is] bit_is(up configuration) + cd_a[is] bit_is(dw configuration),
+ *     mean[a]  = <psi|O_a|psi> / <psi|psi>   (always returned),    m_a = mean[a] if subtract_mean != 0, else 0,
+ *     norm2[a] = <out_a|out_a>.
+ * S^z_i is cu = +1/2, cd = -1/2 on orbital i; n_i is cu = cd = 1; totals and staggered sums are further rows of coef.  With subtract_mean
+ * the outputs are the fluctuations dO_a|psi>: the start vector AND the probes of hxv_lanczos_tridiag_probes for
+ *     chi_ab(z) = - sum_n [ w_n[a] / (z - e_n) - conj(w_n[a]) / (z + e_n) ],   e_n = poles[n] - E,
+ * w_n[a] the weights hxv_gf_from_probes returns for the run started from out_b with the probes out_a and norm = sqrt(norm2[b]), E the
+ * energy of psi (INTEGRATION.md section 4 has the call order, the thermal sum and the cutoff that drops the rounding ghosts of psi at e_n = 0).
+ *   coef    : host, [nops][2][Nimp] doubles: for every operator cu[0..Nimp) then cd[0..Nimp).
+ *   d_psi   : a device vector of h (this rank's slab in the padded layout, device row order included); pad rows are never read; unchanged.
+ *   d_out   : host list of nops device vectors of h, all different and none of them d_psi; every element is written, pad rows as zero.
+ * Two passes: the first reads psi once for all operators (the nops + 1 sums), the second reads it once more, writes the nops vectors and
+ * sums their norms: 16 + (16 + 16 nops) bytes per basis state.  A diagonal operator keeps the row and the basis sign of a device row
+ * cancels, so a device row order only changes where the occupations are looked up.  No floating-point atomics and a fixed work list: the
+ * same inputs on the same handle give the same bits on every call.  The scratch (a few KB) comes from the device-buffer cache and goes back
+ * before the call returns; the occupation words are built on first use and kept with the sector image.  Runs on the handle's stream and
+ * returns when the scalars are on the host.
+ * SPLIT SECTORS (after hxv_comm_init / hxv_comm_init_local): collective; d_psi and the outputs are this rank's slabs; the nops + 1 sums of
+ * the first pass travel in ONE all-reduce, the nops norms of the second in ONE more, and every rank returns the global numbers.  A failure
+ * of one rank's own arguments or resources is agreed on before the first collective step: every rank returns an error, nobody waits.
+ * Errors (nothing is written): HXV_ERR_ARG for NULL arguments, nops outside [1, HXV_MAX_DENSITY_OPS], a NULL or repeated output, an output
+ * equal to d_psi, a coefficient that is not finite, a state that is zero or not finite; HXV_ERR_STATE for handles without basis maps (from
+ * CSR, dw panels) and for a split sector without its communicator; HXV_ERR_UNSUPPORTED for Nimp > 10.                                  */
+#define HXV_MAX_DENSITY_OPS 8
+int hxv_apply_density_ops(hxv_handle *h, int32_t nops, const double *coef /* [nops][2][Nimp]: cu then cd, is = iorb + ilat*Norb */,
+                          int32_t subtract_mean, const void *d_psi, void *const *d_out /* nops device vectors of h */,
+                          double *mean /* [nops] */, double *norm2 /* [nops] */);
+
 /* ---- device vectors owned by the library --------------------------------------------------------------------------------
  * For host programs without a HIP binding of their own (the Fortran glue): a local vector of the handle's sector in the padded device
  * layout (hxv_localvec_elems() complex elements, zeroed), from the engine's buffer cache.  Such a pointer is what the device drivers take
