@@ -109,6 +109,7 @@ struct TableArena {
 // the tile plan of the default options and every device table of both.  Handles SHARE it (shared_ptr): the reference re-opens the
 // same sector for every Green's-function channel (build_Hv_sector / delete_Hv_sector around each sp_lanc_tridiag, ED_GF_NORMAL.f90:208-222),
 // and the images of closed sectors stay in a per-process cache keyed by everything that determines them (hxv_capi.hip: sector_cache).
+struct PtTables;
 struct SectorImage {
   SectorHost host;
   DevSector dev{};
@@ -128,14 +129,12 @@ struct SectorImage {
   struct ObsTables;
   std::shared_ptr<ObsTables> obs;
   std::mutex obs_mu;
-  // the bath-group tables and the work list of the cluster density matrix (hxv_cluster_dm.hip), built on the first hxv_cluster_dm_accumulate
-  struct CdmTables;
-  std::shared_ptr<CdmTables> cdm;
+  // the partial-trace tables (hxv_partial_trace.hip) of the cluster density matrix, built on the first hxv_cluster_dm_accumulate
+  std::shared_ptr<PtTables> cdm;
   std::mutex cdm_mu;
-  // the group tables and work lists of the subset density matrices (hxv_reduced_dm.hip), one per (orbital mask, sign convention) asked for,
-  // most recently used last, a few at most; built by hxv_reduced_dm_accumulate
-  struct RdmTables;
-  std::vector<std::pair<uint64_t, std::shared_ptr<RdmTables>>> rdm;
+  // those of the subset density matrices (hxv_reduced_dm.cpp), one per (orbital mask, sign convention) asked for, most recently used last, a
+  // few at most; built by hxv_reduced_dm_accumulate
+  std::vector<std::pair<uint64_t, std::shared_ptr<PtTables>>> rdm;
   std::mutex rdm_mu;
   // the impurity-occupation words of the density-type operators (hxv_density_ops.hip), built on the first hxv_apply_density_ops
   struct DopTables;

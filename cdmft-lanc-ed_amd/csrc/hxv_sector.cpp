@@ -16,18 +16,11 @@
 #include <thread>
 
 #include "hxv_internal.hpp"
+#include "hxv_partial_trace_host.hpp"  // binom
 
 namespace hxv {
 
 namespace {
-
-int64_t binom(int n, int k) {
-  if (k < 0 || k > n) return 0;
-  k = std::min(k, n - k);
-  int64_t r = 1;
-  for (int i = 1; i <= k; ++i) r = r * (n - k + i) / i;
-  return r;
-}
 
 // ascending list of ns-bit integers with popcount n (Gosper's hack)
 std::vector<uint32_t> make_map(int ns, int n) {
