@@ -18,7 +18,8 @@
 //               bit = the Fermi parity
 //   replay      rho formed from the tables by plain loops (class -> pair -> outer product -> dense matrix), summed over the ranks, against
 //               the partial trace taken straight from the basis maps: within 1e-13 at trace 0.7
-// Nothing here calls a helper of the builder or of the enumerations.  Output: one line "CASE ..." per (SPEC, rank count).  Exit status 0, or
+// Nothing here calls a helper of the builder or of the enumerations.  Output: one line "CASE ..." per (SPEC, rank count), and one line
+// "REACH ..." with the paths the 256-CU work list makes the tile kernel take.  Exit status 0, or
 // 1 with the first failed check on stderr; abort() from the accessor on an out-of-range table read.
 #include <algorithm>
 #include <cinttypes>
@@ -309,6 +310,47 @@ void check_rank(const SectorHost& s, const Spec& sp, uint32_t S, int nsub, const
   }
 }
 
+// which paths of pt_tile_kernel the work list of one rank makes it take (read from items / cls as the kernel reads them): printed as a
+// "REACH" line per (SPEC, rank count) for the 256-CU tables, for the coverage table of LABNOTES.md (scripts/partial_trace_reach.py)
+struct Reach {
+  int64_t t2_items = 0, t4_items = 0;
+  int tile_classes = 0, classes_second_trip = 0;  // tile-kernel classes; those with an item whose batch loop takes a second trip
+  int max_batches = 0;                            // most trips of the batch loop over one dw group of one item
+  int t4_max_bc = 0, nrep4_max_bc = 0;            // most pairs staged at once by a <4,2> item / by an item of a four-wave class
+  int max_groups = 0, max_rounds = 0;             // most dw groups one tile item spans; most staging rounds of one batch
+  void take(const Reach& o) {
+    t2_items += o.t2_items, t4_items += o.t4_items;
+    tile_classes = std::max(tile_classes, o.tile_classes), classes_second_trip = std::max(classes_second_trip, o.classes_second_trip);
+    max_batches = std::max(max_batches, o.max_batches), t4_max_bc = std::max(t4_max_bc, o.t4_max_bc);
+    nrep4_max_bc = std::max(nrep4_max_bc, o.nrep4_max_bc), max_groups = std::max(max_groups, o.max_groups);
+    max_rounds = std::max(max_rounds, o.max_rounds);
+  }
+};
+Reach reach_of(const PtHostTables& t) {
+  Reach r;
+  std::vector<char> second(t.cls.size(), 0), tile(t.cls.size(), 0);
+  for (size_t k = (size_t)t.nitems[0]; k < t.items.size(); ++k) {
+    const PtItem& it = t.items[k];
+    const PtClass& c = t.cls[(size_t)it.cls];
+    const bool t4 = k >= (size_t)(t.nitems[0] + t.nitems[1]);
+    (t4 ? r.t4_items : r.t2_items) += 1;
+    tile[(size_t)it.cls] = 1;
+    const int gd0 = it.p0 / c.ngu, gd1 = (it.p1 - 1) / c.ngu;
+    r.max_groups = std::max(r.max_groups, gd1 - gd0 + 1);
+    for (int gd = gd0; gd <= gd1; ++gd) {
+      const int lo = gd == gd0 ? it.p0 - gd0 * c.ngu : 0, hi = gd == gd1 ? it.p1 - gd1 * c.ngu : c.ngu;
+      const int nb = (hi - lo + c.batch - 1) / c.batch, bc = std::min(c.batch, hi - lo);
+      r.max_batches = std::max(r.max_batches, nb);
+      if (nb > 1) second[(size_t)it.cls] = 1;
+      if (t4) r.t4_max_bc = std::max(r.t4_max_bc, bc);
+      if (c.nrep > 1) r.nrep4_max_bc = std::max(r.nrep4_max_bc, bc);
+      r.max_rounds = std::max(r.max_rounds, (bc * c.du + PT_THREADS - 1) / PT_THREADS);
+    }
+  }
+  for (size_t c = 0; c < t.cls.size(); ++c) r.tile_classes += tile[c], r.classes_second_trip += second[c];
+  return r;
+}
+
 // one SPEC on the sectors of the ranks of one split
 void run_case(const std::vector<SectorHost>& ranks, int nimp, const Spec& sp, const std::vector<cd>& psi) {
   const SectorHost& s0 = ranks[0];
@@ -321,6 +363,7 @@ void run_case(const std::vector<SectorHost>& ranks, int nimp, const Spec& sp, co
   for (uint32_t m : s0.map_dw) par.dw.push_back((uint8_t)(sp.fermi ? fermi_parity(m, S) : 0u));
   const std::vector<cd> ref = direct(s0, S, nsub, par, psi);
   Totals tot;
+  Reach reach;
   for (int ncu : {256, 1}) {
     std::vector<uint8_t> seen((size_t)s0.dimup * s0.dimdw, 0);
     std::vector<cd> rho((size_t)(nn * nn));
@@ -335,8 +378,15 @@ void run_case(const std::vector<SectorHost>& ranks, int nimp, const Spec& sp, co
       REQUIRE(e.empty(), "pt_build: %s", e.c_str());
       check_rank(s, sp, S, nsub, t, par, psi, s.rank ? &rank0 : nullptr, seen, rho, tot);
       if (s.rank == 0) rank0 = t;
+      if (ncu == 256) reach.take(reach_of(t));
     }
     g_case = fmt("%s nranks=%d ncu=%d", sp.text.c_str(), nranks, ncu);
+    if (ncu == 256) {  // (before the replay's verdict: the line describes the work list, whatever becomes of the sums)
+      printf("REACH spec=%s nranks=%d ncu=256 t2_items=%" PRId64 " t4_items=%" PRId64 " tile_classes=%d classes_second_trip=%d max_batches=%d t4_max_bc=%d nrep4_max_bc=%d max_groups=%d max_rounds=%d\n",
+           sp.text.c_str(), nranks, reach.t2_items, reach.t4_items, reach.tile_classes, reach.classes_second_trip, reach.max_batches, reach.t4_max_bc,
+           reach.nrep4_max_bc, reach.max_groups, reach.max_rounds);
+      fflush(stdout);
+    }
     for (size_t k = 0; k < seen.size(); ++k)
       REQUIRE(seen[k] == 1, "(row %zu, column %zu) is named by no pair of any rank", k % (size_t)s0.dimup, k / (size_t)s0.dimup);
     double err = 0, tr = 0;
