@@ -27,20 +27,23 @@ enum LzSlot : int {
   LZ_ALPHA_S = 4,  // alpha*s: coefficient of the stored vector in the subtract-and-norm pass
   LZ_TMP = 5,      // norms and checks outside the recurrence
   LZ_STEP = 6,     // step counter of the device-only iterations (lz_next)
-  LZ_AGREE = 7,    // comm_agree's status all-reduce (hxv_comm.cpp)
+  LZ_AGREE = 7,    // comm_agree's status all-reduce (hxv_transport.cpp)
   LZ_PAIR = 8
 };
 // vector-sized device buffers go through the engine's cache (hxv_pool.cpp): a fresh hipMalloc costs ~25 ms per GB here
 hipError_t pool_alloc(int device, size_t bytes, void** out);
 void pool_free(int device, void* ptr);
 int ensure_wt(hxv_handle* h);                // (re)allocates the dw-hop scratch of the tiled kernels (hxv_capi.hip)
-// slab exchange of a split sector (hxv_comm.cpp)
+// the two rank transports of a split sector and the collectives over them (hxv_transport.cpp)
 bool comm_ready(const hxv_handle* h);
-bool comm_in_gather(const hxv_handle* h, const void* p);  // p lies in one of the handle's gather buffers (hxv_slab_home)
 int comm_allreduce_sum(hxv_handle* h, double* d_buf, size_t count, hipStream_t st);  // no-op without a communicator
 int comm_sendrecv_cols(hxv_handle* h, const void* send, const int64_t* send_ptr, void* recv, const int64_t* recv_ptr, size_t col_bytes, hipStream_t st);
+int comm_allgather_inplace(hxv_handle* h, void* base, size_t slot_bytes, hipStream_t st);  // rank r's slot at base + r * slot_bytes -> every rank's
 int comm_agree(hxv_handle* h, int rc_local);  // collective: non-zero on every rank if any rank passes non-zero (no-op without a communicator)
+void comm_release_transport(hxv_handle* h);   // comm_release's first half: the handle leaves its communicator / its group
 int need_comm(const hxv_handle* h, const char* who);  // HXV_ERR_STATE ("<who> on a split sector needs the communicator...") for a split sector without one
+// slab exchange of a split sector: what the product does with those collectives (hxv_exchange.cpp)
+bool comm_in_gather(const hxv_handle* h, const void* p);  // p lies in one of the handle's gather buffers (hxv_slab_home)
 // this rank's slab -> d_full, every rank's slab at column slot rank*cmax (the padded all-gather layout, whatever exchange mode h uses)
 int comm_allgather_slab(hxv_handle* h, const double2* d_v_local, double2* d_full, hipStream_t st);
 // (H v)|slab from this rank's slab: exchange + product; `ep`: optional Lanczos epilogue of pass A (its partial sums are this rank's share)
@@ -212,22 +215,19 @@ struct hxv_handle {
   int kernel = 1;
   // split sector: RCCL communicator over the nranks handles (hxv_comm_init) and the gathered vector
   void* comm = nullptr;          // ncclComm_t
-  void* comm_shared = nullptr;   // hxv_comm.cpp ProcComm: the PROCESS-level communicator `comm` belongs to (one ncclCommInitRank per process and
+  void* comm_shared = nullptr;   // hxv_transport.cpp ProcComm: the PROCESS-level communicator `comm` belongs to (one ncclCommInitRank per process and
                                  // (nranks, rank, device, library), shared by every sector the process opens; ED_VARS_GLOBAL.f90:365-380 sets MpiComm once
                                  // per solve); null: thread ranks / none
   std::atomic<int> comm_aborted{0};  // hxv_comm_abort has run (from ANOTHER host thread while this rank's own sits in a collective) on `comm` (freed by ncclCommAbort: never destroyed again, never used again)
-  void* comm_api = nullptr;      // the RCCL entry points that communicator was created with (hxv_comm.cpp: the system's librccl, or HXV_RCCL_LIB)
-  void* lgroup = nullptr;        // thread ranks of one process (hxv_comm_init_local): the group object, see hxv_comm.cpp
-  const char* xfer_send = nullptr;         // thread ranks: what this rank offers in the column exchange under way (comm_sendrecv_cols)
-  const int64_t* xfer_send_ptr = nullptr;  //               and its per-destination offsets
-  const double2* xfer_full = nullptr;      // thread ranks: the whole-vector buffer of comm_allgather_slab under way
+  void* comm_api = nullptr;      // the RCCL entry points that communicator was created with (hxv_transport.cpp: the system's librccl, or HXV_RCCL_LIB)
+  void* lgroup = nullptr;        // thread ranks of one process (hxv_comm_init_local): the group object, see hxv_transport.cpp
   double2* d_gather = nullptr;   // nranks * cmax * pitch elements (all-gather layout) / (qdw + halo) * pitch (halo layout)
   double2* d_gather_x[2] = {nullptr, nullptr};  // two more of the same for the device Lanczos on a split sector (three vectors rotate)
-  double2* gather_cur = nullptr; // the gather buffer the exchange under way / last done runs on (peers of a thread group read it)
+  double2* gather_cur = nullptr; // the gather buffer the last exchange ran on (apply_slab reads the gathered vector there)
   int a2a_overlap = 0;           // option "exchange_overlap": exchange mode 2 runs diagonal + up hops on a second stream while the transposes are under way
   hipStream_t stream2 = nullptr; // that second stream and its two events (created on first use)
   hipEvent_t ov_ev[2] = {nullptr, nullptr};
-  void* a2a = nullptr;           // exchange 2 (two all-to-all transposes): panel handle, staging buffers, per-peer offsets (hxv_comm.cpp)
+  void* a2a = nullptr;           // exchange 2 (two all-to-all transposes): panel handle, staging buffers, per-peer offsets (hxv_exchange.cpp)
   int64_t n_slab_copy = 0;       // slab copies into a gather buffer (exchange with a vector that is not at home)
   double2* d_send = nullptr;     // halo exchange: packed columns, grouped by destination rank
   int32_t* d_send_cols = nullptr;

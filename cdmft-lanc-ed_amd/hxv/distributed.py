@@ -1,9 +1,9 @@
 """torch.distributed TWIN of the engine's three slab exchanges -- REHEARSAL CODE, not the product's N>1 path.
 
-Since round 3 the exchanges live behind the C-ABI (csrc/hxv_comm.cpp: hxv_comm_init + hxv_apply_device_slab, RCCL or thread ranks), and
+Since round 3 the exchanges live behind the C-ABI (csrc/hxv_transport.cpp + csrc/hxv_exchange.cpp: hxv_comm_init + hxv_apply_device_slab, RCCL or thread ranks), and
 since round 4 `bench.py --gpus N` uses nothing else on its default `--backend nccl` path.  This module stays for `bench.py --backend gloo`
 and tests/test_distributed_gloo.py: the partitioning, the equal-count all-gather layout, the halo plan and the two transposes exercised at
-world sizes 2-4 on the CPU, where no GPU (and no RCCL) is needed.  A change of the exchange logic is made in hxv_comm.cpp and mirrored here.
+world sizes 2-4 on the CPU, where no GPU (and no RCCL) is needed.  A change of the exchange logic is made in hxv_exchange.cpp and mirrored here.
 
 DimDw-sharded HxV across the GPUs of one node: one process per GPU, torch.distributed as the plumbing.
 

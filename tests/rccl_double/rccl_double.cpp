@@ -1,6 +1,6 @@
-// TEST-ONLY double of the RCCL entry points the engine resolves (ten, plus ncclCommAbort) (csrc/hxv_comm.cpp: rccl()), for ranks that are host THREADS of one
+// TEST-ONLY double of the RCCL entry points the engine resolves (ten, plus ncclCommAbort) (csrc/hxv_transport.cpp: rccl()), for ranks that are host THREADS of one
 // process sharing one GPU -- RCCL itself refuses two ranks on one device, and no round of this project has had a second GPU.  It exists
-// so that the RCCL branches of hxv_comm.cpp (the grouped ncclSend / ncclRecv of the column exchange and of both transposes, the in-place
+// so that the RCCL branches of hxv_transport.cpp (the grouped ncclSend / ncclRecv of the column exchange and of both transposes, the in-place
 // ncclAllGather, the ncclSum / ncclMax all-reduces) EXECUTE with 2-4 ranks and are checked against the oracle: counts, offsets and
 // pointers are the engine's, only the transport underneath is replaced.  Loaded through HXV_RCCL_LIB; never linked into the product.
 //

@@ -1,4 +1,4 @@
-// TEST-ONLY double of the ten RCCL entry points the engine resolves (csrc/hxv_comm.cpp: rccl()) for ranks that are separate PROCESSES
+// TEST-ONLY double of the ten RCCL entry points the engine resolves (csrc/hxv_transport.cpp: rccl()) for ranks that are separate PROCESSES
 // sharing ONE GPU -- the process model of `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`, which RCCL itself refuses
 // on one device.  Companion of rccl_double.cpp (thread ranks of one process).  Loaded through HXV_RCCL_LIB; never linked into the product.
 //

@@ -1,10 +1,10 @@
-"""SEVERAL ranks of a split sector on ONE GPU: the thread-rank transport of csrc/hxv_comm.cpp (hxv_comm_init_local) runs the
+"""SEVERAL ranks of a split sector on ONE GPU: the thread-rank transport of csrc/hxv_transport.cpp (hxv_comm_init_local) runs the
 multi-rank code of the C-ABI for real -- slab copies into the all-gather layout, uneven splits, halo lists and offsets, the
 drivers' all-reduces, the fused recurrence and the REAL-vector mode on slabs, the collective error agreement -- everything but
 RCCL's own transport (RCCL refuses two ranks on one device; librccl has run with one rank only: tests/test_gpu_comm.py).
 Every test runs a second time with transport "rccl_double": the handles join through hxv_comm_unique_id / hxv_comm_init, the path
 one process per GPU takes, with HXV_RCCL_LIB pointing at tests/rccl_double (RCCL's ten entry points for thread ranks of one process),
-so the RCCL branches of hxv_comm.cpp -- the counts, offsets and pointers of the grouped ncclSend / ncclRecv in the halo exchange, both
+so the RCCL branches of hxv_transport.cpp -- the counts, offsets and pointers of the grouped ncclSend / ncclRecv in the halo exchange, both
 transposes and the ladder operators, the in-place ncclAllGather, the ncclSum all-reduces, the ncclMax error agreement -- execute
 with 2-4 ranks against the same references.
 Reference semantics: spMatVec_MPI_main (ED_HAMILTONIAN_SPARSE_HxV.f90:230-315), the DimDw split of ED_HAMILTONIAN.f90:93-105,
