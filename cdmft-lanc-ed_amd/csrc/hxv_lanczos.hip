@@ -1,6 +1,6 @@
 // Device Lanczos behind the C-ABI (include/hxv.h): the single-vector recurrences with the SciFortran call shapes
 // (sp_lanc_tridiag, sp_lanc_eigh; ED_GF_NORMAL.f90:215-220, ED_DIAG.f90:176-184), the tridiagonalisation with probe overlaps, the paired
-// tridiagonalisation and the iteration timer of bench.py.  (The Green's-function start vectors, c / c^dagger on the ground state, are
+// tridiagonalisation with and without them and the iteration timer of bench.py.  (The Green's-function start vectors, c / c^dagger on the ground state, are
 // hxv_ladder.hip's.)
 // Every driver -- and the local step hxv_eigh_lowest borrows -- takes its fused iteration from ONE function, fused_step_enqueue; the drivers
 // differ in who provides s and c (a host upload, or lz_next on the device), in whether there is a previous vector, and in what they read back.
@@ -711,27 +711,38 @@ int hxv_lanczos_eigh(hxv_handle* h, int32_t nitermax, double threshold, double* 
   return HXV_OK;
 }
 
+namespace {
+// THE paired driver behind hxv_lanczos_tridiag_pair (nprobes = 0) and hxv_lanczos_tridiag_pair_probes.
 // Two REAL Lanczos runs on one complex product (real H): the start vectors travel as real and imaginary part of one
 // complex vector -- H(x + i y) = H x + i H y -- and every scalar of the recurrence exists once per component.  The channels of
 // one Green's-function solve are independent (ED_GF_NORMAL.f90:123-306: one sp_lanc_tridiag per channel), so two of them share
 // the product's passes.  The arithmetic of each component is, operation for operation, that of hxv_lanczos_tridiag on (x, 0)
 // through the same kernels (options real_vectors = 0, job_up = 0): alanc/blanc are bit-identical to two such runs.
-int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_vin_b, int32_t nlanc, double* alanc_a, double* blanc_a,
-                             double* alanc_b, double* blanc_b, double threshold, int32_t* nsteps_a, int32_t* nsteps_b) {
-  if (!h || !d_vin_a || !d_vin_b || nlanc < 1 || !alanc_a || !blanc_a || !alanc_b || !blanc_b)
-    return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair: bad argument");
-  if (const char* why = real_mode_blocker(h)) return fail(HXV_ERR_UNSUPPORTED, std::string("hxv_lanczos_tridiag_pair: unavailable: ") + why);
+// With probes (real ones, shared by both components; converted once into pooled double[qdw][pitch] buffers) the overlaps of the STORED
+// complex vector are taken before each step's product, as in tridiag_run, by lz_probe_dots_pair: overlaps_x as hxv_lanczos_tridiag_probes
+// lays them out, imaginary parts zero.  rc_args: what the entry decided from its own arguments; it goes into the agreement in front of the
+// first collective.  The imaginary parts of the start vectors AND of the probes are checked in ONE reduction, whose sum every rank sees.
+int tridiag_pair_run(hxv_handle* h, const char* who, int rc_args, const void* d_vin_a, const void* d_vin_b, int nprobes,
+                     const void* const* d_probes, int nlanc, double* alanc_a, double* blanc_a, double* overlaps_a, double* alanc_b,
+                     double* blanc_b, double* overlaps_b, double threshold, int32_t* nsteps_a, int32_t* nsteps_b) {
+  if (const char* why = real_mode_blocker(h)) return fail(HXV_ERR_UNSUPPORTED, std::string(who) + ": unavailable: " + why);
   if (int rcc = need_comm(h, "device Lanczos")) return rcc;
-  if (!h->lz_fused) return fail(HXV_ERR_UNSUPPORTED, "hxv_lanczos_tridiag_pair needs the fused recurrence (option lanczos_fused)");
+  if (!h->lz_fused) return fail(HXV_ERR_UNSUPPORTED, std::string(who) + " needs the fused recurrence (option lanczos_fused)");
   HIPCHK(hipSetDevice(h->device));
-  PoolGuard pooled{h, {}};
+  PoolGuard pooled{h, {}};  // (staged start vectors; with probes their real copies and the scratch of the check and the overlaps)
   const int64_t n = lz_len(h, false);
   const int g = grid_for(n);
   // scalars: the LzSlot block of component a, the one of b LZ_PAIR behind it (the handle's d_scalars has room for one only); the block
   // partials of the start vectors' check behind them
   DevFree sc_mem{h->stream};
+  // scratch of a run WITH probes, from the device-buffer cache and sized by nprobes: block partials of Im^2 (start vectors, then one row of
+  // RED_BLOCKS per probe, g of each used, side by side for the one reduction), block partials and sums of a step's overlaps
+  double* d_ws = nullptr;
+  const size_t n_chk = (size_t)(1 + std::max(nprobes, 0)) * RED_BLOCKS, n_part = (size_t)2 * std::max(nprobes, 0) * RED_BLOCKS;
+  LzRealProbes pr{};
   // every rank-local preparation that can fail comes BEFORE the agreement: a rank that cannot go on makes all ranks return
   auto prepare = [&]() -> int {
+    if (rc_args) return rc_args;
     int r = stage_start_vector(h, d_vin_a, pooled);  // (start vectors at hxv_slab_home: staged before their home is cleared)
     if (!r) r = stage_start_vector(h, d_vin_b, pooled);
     if (!r) r = ensure_lz(h, false);  // (split sector: vectors are this rank's slab, every sum below is all-reduced)
@@ -739,26 +750,46 @@ int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_v
     if (!r) r = ensure_lz_partial(h, 2 * lz_pass_a_workgroups(h, false));
     if (r) return r;
     HIPCHK(hipMalloc((void**)&sc_mem.p, (size_t)(2 * LZ_PAIR + 3 * RED_BLOCKS) * sizeof(double)));
+    if (nprobes == 0) return HXV_OK;
+    if ((r = pooled.take((n_chk + n_part + 2 * nprobes) * sizeof(double), (void**)&d_ws))) return r;
+    for (int j = 0; j < nprobes; ++j)
+      if ((r = pooled.take((size_t)std::max<int64_t>(n, 1) * sizeof(double), (void**)&pr.p[j]))) return r;
+    // page-locked staging for the overlaps of every step (a slot of 2*nprobes sums per step), shared with tridiag_run
+    const int64_t want = (int64_t)2 * nprobes * nlanc;
+    if (want > h->probe_ov_n) {
+      if (h->h_probe_ov) (void)hipHostFree(h->h_probe_ov);
+      h->h_probe_ov = nullptr;
+      h->probe_ov_n = 0;
+      HIPCHK(hipHostMalloc((void**)&h->h_probe_ov, (size_t)want * sizeof(double), hipHostMallocDefault));
+      h->probe_ov_n = want;
+    }
     return HXV_OK;
   };
   int rc = comm_agree(h, prepare());
   if (rc) return rc;
   double* const d_sc = sc_mem.p;
-  double* d_p0 = d_sc + 2 * LZ_PAIR;
-  double* d_p1 = d_p0 + RED_BLOCKS;
+  double* d_p0 = nprobes ? d_ws : d_sc + 2 * LZ_PAIR;  // (Im^2 of the start vectors; the probes' rows follow it at a distance of g)
+  double* d_p1 = d_sc + 2 * LZ_PAIR + RED_BLOCKS;
   double* d_p2 = d_p1 + RED_BLOCKS;
+  double *d_part = d_ws + n_chk, *d_ov = d_part + n_part;
   HIPCHK(hipMemsetAsync(d_sc, 0, 2 * LZ_PAIR * sizeof(double), h->stream));
   double2 *q = h->lz_vec[0], *qm = h->lz_vec[1], *w = h->lz_vec[2];
   hipLaunchKernelGGL(lz_pack_pair, dim3(g), dim3(256), 0, h->stream, n, (const double2*)d_vin_a, (const double2*)d_vin_b, q, d_p0, d_p1, d_p2);
+  for (int j = 0; j < nprobes; ++j)
+    hipLaunchKernelGGL(lz_probe_real_pc, dim3(g), dim3(256), 0, h->stream, n, h->host.dimup, h->host.pitch, (const double2*)d_probes[j],
+                       const_cast<double*>(pr.p[j]), d_p0 + (size_t)(1 + j) * g);
   // (its own block: the three sums of the check sit in a row from LZ_TMP on)
-  if ((rc = reduce_scalar(h, d_p0, g, LZ_TMP, 0, d_sc)) || (rc = reduce_scalar(h, d_p1, g, LZ_TMP + 1, 1, d_sc)) || (rc = reduce_scalar(h, d_p2, g, LZ_TMP + 2, 1, d_sc))) return rc;
+  if ((rc = reduce_scalar(h, d_p0, (1 + nprobes) * g, LZ_TMP, 0, d_sc)) || (rc = reduce_scalar(h, d_p1, g, LZ_TMP + 1, 1, d_sc)) || (rc = reduce_scalar(h, d_p2, g, LZ_TMP + 2, 1, d_sc))) return rc;
   double head[3];
   HIPCHK(hipMemcpyAsync(head, d_sc + LZ_TMP, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (head[0] != 0.0) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair: the start vectors must be real (zero imaginary parts)");
+  // (head[0] is the sum over all ranks: every rank returns here together)
+  if (head[0] != 0.0)
+    return fail(HXV_ERR_ARG, std::string(who) + (nprobes ? ": the start vectors and the probes must be real (zero imaginary parts)" : ": the start vectors must be real (zero imaginary parts)"));
   for (int c = 0; c < 2; ++c)
-    if (!(head[1 + c] > 0.0) || !std::isfinite(head[1 + c])) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair: a start vector is zero or not finite");
+    if (!(head[1 + c] > 0.0) || !std::isfinite(head[1 + c])) return fail(HXV_ERR_ARG, std::string(who) + ": a start vector is zero or not finite");
   for (int k = 0; k < nlanc; ++k) alanc_a[k] = blanc_a[k] = alanc_b[k] = blanc_b[k] = 0.0;
+  for (size_t i = 0; i < (size_t)2 * nlanc * nprobes; ++i) overlaps_a[i] = overlaps_b[i] = 0.0;
   // per component, LzRunner's fused recurrence: q = s*X, s = 1/beta_k (the start vector's norm carried as beta_0)
   LzScale scale[2];
   bool alive[2] = {true, true};
@@ -766,8 +797,19 @@ int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_v
   for (int c = 0; c < 2; ++c) scale[c].begin(start_norm(head[1 + c]));
   double* al[2] = {alanc_a, alanc_b};
   double* bl[2] = {blanc_a, blanc_b};
+  double* ovl[2] = {overlaps_a, overlaps_b};
   bool first = true;
   for (int k = 0; k < nlanc && (alive[0] || alive[1]); ++k) {
+    const double* stage = nullptr;
+    if (nprobes > 0) {
+      // the overlaps of the STORED vector X_k, enqueued before the step that overwrites nothing of it; their copy to the host completes with
+      // the synchronisation the step makes for alpha and beta.  One all-reduce for the 2*nprobes sums of a split sector.
+      double* slot = h->h_probe_ov + (size_t)2 * nprobes * k;  // (a slot per step: nothing is overwritten while a copy is in flight)
+      launch_probe_dots_pair(g, h->stream, nprobes, n, q, pr, d_part, d_ov);
+      if ((rc = comm_allreduce_sum(h, d_ov, (size_t)2 * nprobes, h->stream))) return rc;
+      HIPCHK(hipMemcpyAsync(slot, d_ov, (size_t)2 * nprobes * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      stage = slot;
+    }
     double up[2][2];  // -> LZ_S, LZ_C of each component (a finished one is multiplied away: the other one goes on alone)
     for (int c = 0; c < 2; ++c) {
       up[c][0] = alive[c] ? scale[c].s_cur : 0.0;
@@ -780,6 +822,8 @@ int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_v
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int c = 0; c < 2; ++c) {
       if (!alive[c]) continue;
+      // q_k = s * X_k with the s of BEFORE the step (up[c][0]); the imaginary slots stay zero
+      for (int j = 0; j < nprobes; ++j) ovl[c][2 * ((size_t)k * nprobes + j)] = stage[2 * j + c] * up[c][0];
       const double a = host[c * LZ_PAIR + LZ_ALPHA], bt = host[c * LZ_PAIR + LZ_BETA];
       al[c][k] = a;
       if (k + 1 < nlanc) bl[c][k + 1] = bt;
@@ -802,6 +846,36 @@ int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_v
   if (nsteps_a) *nsteps_a = done[0];
   if (nsteps_b) *nsteps_b = done[1];
   return HXV_OK;
+}
+}  // namespace
+
+int hxv_lanczos_tridiag_pair(hxv_handle* h, const void* d_vin_a, const void* d_vin_b, int32_t nlanc, double* alanc_a, double* blanc_a,
+                             double* alanc_b, double* blanc_b, double threshold, int32_t* nsteps_a, int32_t* nsteps_b) {
+  if (!h || !d_vin_a || !d_vin_b || nlanc < 1 || !alanc_a || !blanc_a || !alanc_b || !blanc_b)
+    return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair: bad argument");
+  return tridiag_pair_run(h, "hxv_lanczos_tridiag_pair", HXV_OK, d_vin_a, d_vin_b, 0, nullptr, nlanc, alanc_a, blanc_a, nullptr, alanc_b, blanc_b,
+                          nullptr, threshold, nsteps_a, nsteps_b);
+}
+
+// Two probe runs on one product (include/hxv.h): hxv_lanczos_tridiag_pair with the overlaps of hxv_lanczos_tridiag_probes for each component.
+int hxv_lanczos_tridiag_pair_probes(hxv_handle* h, const void* d_vin_a, const void* d_vin_b, int32_t nprobes, const void* const* d_probes,
+                                    int32_t nlanc, double* alanc_a, double* blanc_a, double* overlaps_a, double* alanc_b, double* blanc_b,
+                                    double* overlaps_b, double threshold, int32_t* nsteps_a, int32_t* nsteps_b) {
+  if (!h) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair_probes: NULL handle");
+  auto check_args = [&]() -> int {
+    if (!d_vin_a || !d_vin_b || nlanc < 1 || !alanc_a || !blanc_a || !alanc_b || !blanc_b)
+      return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair_probes: bad argument (NULL start vector or output, or nlanc < 1)");
+    if (nprobes < 0 || nprobes > HXV_MAX_PROBES) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair_probes: nprobes must be 0 .. HXV_MAX_PROBES (8)");
+    if (nprobes > 0 && (!d_probes || !overlaps_a || !overlaps_b)) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair_probes: nprobes > 0 needs the probe list and both overlaps arrays");
+    for (int j = 0; j < nprobes; ++j) {
+      if (!d_probes[j]) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair_probes: NULL entry in the probe list");
+      // (ensure_lz clears the slab's place in the gather buffers; a START vector there is staged, a probe is the caller's to keep elsewhere)
+      if (comm_ready(h) && comm_in_gather(h, d_probes[j])) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair_probes: a probe lies in a gather buffer of the handle (hxv_slab_home): the driver clears that place");
+    }
+    return HXV_OK;
+  };
+  return tridiag_pair_run(h, "hxv_lanczos_tridiag_pair_probes", check_args(), d_vin_a, d_vin_b, nprobes, d_probes, nlanc, alanc_a, blanc_a,
+                          overlaps_a, alanc_b, blanc_b, overlaps_b, threshold, nsteps_a, nsteps_b);
 }
 
 namespace {

@@ -209,6 +209,64 @@ __global__ void __launch_bounds__(256) lz_probe_final(const double* __restrict__
   }
 }
 
+// PROBE OVERLAPS OF A PAIRED RUN (hxv_lanczos_tridiag_pair_probes): x holds two real Lanczos vectors as (re, im) = (a, b), the M probes are
+// REAL vectors on the complex slab's index (double[qdw][pitch], written once per call by lz_probe_real_pc), shared by both components.
+// partial[block][2M]: (a_j, b_j) = partial sums of p_j * x.re and p_j * x.im.  One element per thread and iteration, each product rounded
+// before it is added: with p.y = x.y = 0 lz_probe_dots<M, false> adds exactly these terms in this order (fma(0, 0, t) == t), so component a's
+// sums carry the bits of the single run's complex path; 16 + 8M bytes per state where that kernel reads 16 + 16M.
+struct LzRealProbes {
+  const double* p[HXV_MAX_PROBES];
+};
+template <int M>
+__global__ void __launch_bounds__(256) lz_probe_dots_pair(int64_t n, const double2* __restrict__ x, LzRealProbes pr, double* __restrict__ partial) {
+  double ra[M], rb[M];
+#pragma unroll
+  for (int j = 0; j < M; ++j) ra[j] = rb[j] = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const double2 a = x[i];
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      const double p = pr.p[j][i];
+      {
+#pragma clang fp contract(off)
+        const double t = p * a.x, u = p * a.y;
+        ra[j] = ra[j] + t;
+        rb[j] = rb[j] + u;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    const double sa = block_sum(ra[j]);
+    __syncthreads();  // (block_sum's buffer is read by every thread: the next sum must not overwrite it before)
+    const double sb = block_sum(rb[j]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      partial[(size_t)blockIdx.x * (2 * M) + 2 * j] = sa;
+      partial[(size_t)blockIdx.x * (2 * M) + 2 * j + 1] = sb;
+    }
+  }
+}
+// dst[i] = Re src[i] on the complex slab's own index (n = qdw * pitch elements: the index of the paired Lanczos vector), pad rows
+// (row >= dimup) written as zero whatever the caller left there; partial = per-block sum of Im^2 over the rows below dimup.  Once per call
+// and probe.
+__global__ void __launch_bounds__(256) lz_probe_real_pc(int64_t n, int dimup, int pitch, const double2* __restrict__ src, double* __restrict__ dst,
+                                                        double* __restrict__ partial) {
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int row = (int)(i % pitch);
+    double re = 0.0;
+    if (row < dimup) {
+      const double2 z = src[i];
+      re = z.x;
+      acc += z.y * z.y;
+    }
+    dst[i] = re;
+  }
+  const double sum = block_sum(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
+}
+
 // q = w / scal[ib]
 __global__ void __launch_bounds__(256) lz_scale(int64_t n, double2* q, const double2* w,
                                                 const double* __restrict__ scal, int ib) {
@@ -337,6 +395,26 @@ void launch_probe_dots(int g, hipStream_t st, int m, int64_t n, const double2* x
 #define HXV_PROBE_CASE(M) \
   case M:                 \
     hipLaunchKernelGGL((lz_probe_dots<M, REAL>), dim3(g), dim3(256), 0, st, n, x, pr, d_part); \
+    break;
+    HXV_PROBE_CASE(1)
+    HXV_PROBE_CASE(2)
+    HXV_PROBE_CASE(3)
+    HXV_PROBE_CASE(4)
+    HXV_PROBE_CASE(5)
+    HXV_PROBE_CASE(6)
+    HXV_PROBE_CASE(7)
+    HXV_PROBE_CASE(8)
+#undef HXV_PROBE_CASE
+  }
+  hipLaunchKernelGGL(lz_probe_final, dim3(1), dim3(256), 0, st, d_part, g, 2 * m, d_out);
+}
+// out[2*j], out[2*j+1] = <p_j|Re x>, <p_j|Im x> of this rank's share for the m REAL probes of a paired run: lz_probe_dots_pair<m> on g workgroups,
+// then lz_probe_final as above.  d_part: g * 2m doubles.
+inline void launch_probe_dots_pair(int g, hipStream_t st, int m, int64_t n, const double2* x, const LzRealProbes& pr, double* d_part, double* d_out) {
+  switch (m) {
+#define HXV_PROBE_CASE(M) \
+  case M:                 \
+    hipLaunchKernelGGL((lz_probe_dots_pair<M>), dim3(g), dim3(256), 0, st, n, x, pr, d_part); \
     break;
     HXV_PROBE_CASE(1)
     HXV_PROBE_CASE(2)

@@ -42,6 +42,8 @@ module ED_HAMILTONIAN_GPU_HXV
   !off-diagonal Green's functions from one run per orbital (include/hxv.h: hxv_lanczos_tridiag_probes, hxv_gf_from_probes)
   public :: gpu_sp_lanc_tridiag_probes_dev
   public :: gpu_gf_from_probes
+  !two probe runs on one product (real H; include/hxv.h: hxv_lanczos_tridiag_pair_probes)
+  public :: gpu_sp_lanc_tridiag_pair_probes_dev
   public :: gpu_apply_density_ops_dev
   public :: gpu_vector_to_host
   public :: gpu_vector_from_host
@@ -306,6 +308,17 @@ module ED_HAMILTONIAN_GPU_HXV
        real(c_double),value      :: threshold
        integer(c_int32_t)        :: nsteps
      end function hxv_lanczos_tridiag_probes
+     integer(c_int) function hxv_lanczos_tridiag_pair_probes(h,d_vin_a,d_vin_b,nprobes,d_probes,nlanc,alanc_a,blanc_a,overlaps_a,&
+          alanc_b,blanc_b,overlaps_b,threshold,nsteps_a,nsteps_b) bind(C,name="hxv_lanczos_tridiag_pair_probes")
+       import :: c_int, c_int32_t, c_ptr, c_double, c_double_complex
+       type(c_ptr),value         :: h,d_vin_a,d_vin_b
+       integer(c_int32_t),value  :: nprobes,nlanc
+       type(c_ptr)               :: d_probes(*)
+       real(c_double)            :: alanc_a(*),blanc_a(*),alanc_b(*),blanc_b(*)
+       complex(c_double_complex) :: overlaps_a(*),overlaps_b(*)
+       real(c_double),value      :: threshold
+       integer(c_int32_t)        :: nsteps_a,nsteps_b
+     end function hxv_lanczos_tridiag_pair_probes
      integer(c_int) function hxv_gf_from_probes(nsteps,alanc,blanc,nprobes,overlaps,norm,poles,weights) bind(C,name="hxv_gf_from_probes")
        import :: c_int, c_int32_t, c_double, c_double_complex
        integer(c_int32_t),value  :: nsteps,nprobes
@@ -893,6 +906,48 @@ contains
     if(size(probes)>0)overlaps=ov
     if(present(nsteps))nsteps=int(ns)
   end subroutine gpu_sp_lanc_tridiag_probes_dev
+
+  !> TWO gpu_sp_lanc_tridiag_probes_dev runs on one product per step (real H; include/hxv.h, hxv_lanczos_tridiag_pair_probes): the start
+  !! vectors and the probes are REAL vectors of the open sector (c / c^dagger applied to a real ground state), the probes are shared by both
+  !! runs -- orbitals i, i' of one spin with all c^dagger_j|gs> as probes.  overlaps_x(j,k) = <probes(j)|q_k> of run x, REAL
+  !! (size(probes), size(alanc_x)): the imaginary parts the engine returns are exactly zero and are dropped here.  Columns of steps a run
+  !! did not make are zero; nsteps_x = the steps done.  gpu_gf_from_probes takes cmplx(overlaps_x(:,1:nsteps_x),0d0,8).
+  subroutine gpu_sp_lanc_tridiag_pair_probes_dev(vin_a,vin_b,probes,alanc_a,blanc_a,overlaps_a,alanc_b,blanc_b,overlaps_b,threshold,nsteps_a,nsteps_b)
+    type(gpu_vector),intent(in)  :: vin_a,vin_b
+    type(gpu_vector),intent(in)  :: probes(:)
+    real(8),intent(inout)        :: alanc_a(:),blanc_a(:),alanc_b(:),blanc_b(:)
+    real(8),intent(inout)        :: overlaps_a(:,:),overlaps_b(:,:)
+    real(8),intent(in),optional  :: threshold
+    integer,intent(out),optional :: nsteps_a,nsteps_b
+    real(8)                      :: thr
+    integer(c_int32_t)           :: na,nb
+    type(c_ptr)                  :: plist(8)
+    complex(8),allocatable       :: ova(:,:),ovb(:,:)
+    integer                      :: j
+    if(.not.c_associated(handle))stop "gpu_sp_lanc_tridiag_pair_probes_dev ERROR: Hsector NOT set"
+    if(vin_a%sector_id/=handle_serial.or.vin_b%sector_id/=handle_serial.or..not.c_associated(vin_a%d).or..not.c_associated(vin_b%d))&
+         stop "gpu_sp_lanc_tridiag_pair_probes_dev ERROR: the start vectors do not belong to the open sector"
+    if(size(alanc_a)/=size(alanc_b))stop "gpu_sp_lanc_tridiag_pair_probes_dev ERROR: the two channels need equally long alanc/blanc"
+    if(size(probes)>8)stop "gpu_sp_lanc_tridiag_pair_probes_dev ERROR: more than 8 probes"
+    if(size(overlaps_a,1)/=size(probes).or.size(overlaps_a,2)/=size(alanc_a).or.size(blanc_a)/=size(alanc_a).or.&
+         size(overlaps_b,1)/=size(probes).or.size(overlaps_b,2)/=size(alanc_b).or.size(blanc_b)/=size(alanc_b))&
+         stop "gpu_sp_lanc_tridiag_pair_probes_dev ERROR: overlaps_x must be (size(probes),size(alanc_x)), blanc_x as long as alanc_x"
+    plist=c_null_ptr
+    do j=1,size(probes)
+       if(probes(j)%sector_id/=handle_serial.or..not.c_associated(probes(j)%d))stop "gpu_sp_lanc_tridiag_pair_probes_dev ERROR: a probe does not belong to the open sector"
+       plist(j)=probes(j)%d
+    enddo
+    thr=1d-12; if(present(threshold))thr=threshold
+    allocate(ova(max(size(probes),1),size(alanc_a)),ovb(max(size(probes),1),size(alanc_b)))      !(contiguous, whatever section the caller passed)
+    call check(hxv_lanczos_tridiag_pair_probes(handle,vin_a%d,vin_b%d,int(size(probes),c_int32_t),plist,int(size(alanc_a),c_int32_t),&
+         alanc_a,blanc_a,ova,alanc_b,blanc_b,ovb,thr,na,nb),"gpu_sp_lanc_tridiag_pair_probes_dev")
+    if(size(probes)>0)then
+       overlaps_a=real(ova,8)
+       overlaps_b=real(ovb,8)
+    endif
+    if(present(nsteps_a))nsteps_a=int(na)
+    if(present(nsteps_b))nsteps_b=int(nb)
+  end subroutine gpu_sp_lanc_tridiag_pair_probes_dev
 
   !> Poles and weights from one probes run (include/hxv.h, hxv_gf_from_probes; host code only, the engine's own tridiagonal QL): with
   !! alanc, blanc and overlaps(:,1:nsteps) of gpu_sp_lanc_tridiag_probes_dev and norm = |v| of the unnormalised start vector (sqrt of

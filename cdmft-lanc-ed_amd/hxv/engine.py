@@ -50,7 +50,7 @@ EXPORTS = [
     "hxv_sector_cache_clear", "hxv_sector_cache_stats", "hxv_comm_abort", "hxv_comm_library", "hxv_comm_cache_stats", "hxv_comm_cache_clear", "hxv_host_register", "hxv_host_unregister",
     "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
     "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_reduced_dm_elems", "hxv_reduced_dm_accumulate", "hxv_twin_vector", "hxv_twin_split_plan",
-    "hxv_lanczos_tridiag_probes", "hxv_gf_from_probes", "hxv_apply_density_ops",
+    "hxv_lanczos_tridiag_probes", "hxv_gf_from_probes", "hxv_apply_density_ops", "hxv_lanczos_tridiag_pair_probes",
 ]
 
 _lib = None
@@ -170,6 +170,7 @@ def load_library():
     L.hxv_twin_vector.argtypes = [vp, vp, vp, vp]
     L.hxv_twin_split_plan.argtypes = [i32, i32, i32, i32, pi64, pi64]
     L.hxv_lanczos_tridiag_probes.argtypes = [vp, vp, i32, C.POINTER(vp), i32, pd, pd, pd, dbl, pi32]
+    L.hxv_lanczos_tridiag_pair_probes.argtypes = [vp, vp, vp, i32, C.POINTER(vp), i32, pd, pd, pd, pd, pd, pd, dbl, pi32, pi32]
     L.hxv_gf_from_probes.argtypes = [i32, pd, pd, i32, pd, dbl, pd, pd]
     L.hxv_apply_density_ops.argtypes = [vp, i32, pd, i32, vp, C.POINTER(vp), pd, pd]
     _lib = L
@@ -775,6 +776,31 @@ class HxvSector:
                                                        C.cast(ov.ctypes.data, C.POINTER(C.c_double)) if npr else None, threshold, C.byref(n)),
              "hxv_lanczos_tridiag_probes")
         return a, b, ov[: n.value], n.value
+
+    def lanczos_tridiag_pair_probes(self, vin_a, vin_b, probes, nlanc: int, threshold: float = 1e-12):
+        """hxv_lanczos_tridiag_pair_probes (include/hxv.h): two lanczos_tridiag_probes runs on ONE product per step, real H.  vin_a, vin_b
+        and every probe are REAL device vectors of this sector in the padded layout (complex128 with zero imaginary parts, localElems
+        elements; this rank's slab on a split sector, collective there); both runs share the probes, at most 8, none is allowed.
+        -> ((alanc, blanc, overlaps[nsteps, nprobes] complex128, nsteps) of a, the same of b); the overlaps' imaginary parts are zero."""
+        import torch
+
+        probes = list(probes)
+        for v in [vin_a, vin_b] + probes:
+            if not (torch.is_tensor(v) and v.is_cuda and v.dtype == torch.complex128 and v.is_contiguous() and v.numel() == self.localElems):
+                raise HxvError("lanczos_tridiag_pair_probes takes device vectors in the padded layout (complex128, localElems = "
+                               f"{self.localElems} elements); use pad() / vector_from_host() for a vector in the reference's layout")
+        torch.cuda.synchronize()
+        npr = len(probes)
+        aa, ba, ab, bb = (np.zeros(nlanc) for _ in range(4))
+        ova, ovb = (np.zeros((max(nlanc, 0), npr), dtype=np.complex128) for _ in range(2))
+        na, nb = C.c_int32(), C.c_int32()
+        plist = (C.c_void_p * max(npr, 1))(*[p.data_ptr() for p in probes])
+        pov = lambda ov: C.cast(ov.ctypes.data, C.POINTER(C.c_double)) if npr else None
+        _chk(load_library().hxv_lanczos_tridiag_pair_probes(self._h, vin_a.data_ptr(), vin_b.data_ptr(), npr, plist if npr else None, nlanc,
+                                                            _p(aa, C.c_double), _p(ba, C.c_double), pov(ova), _p(ab, C.c_double), _p(bb, C.c_double),
+                                                            pov(ovb), threshold, C.byref(na), C.byref(nb)),
+             "hxv_lanczos_tridiag_pair_probes")
+        return (aa, ba, ova[: na.value], na.value), (ab, bb, ovb[: nb.value], nb.value)
 
     def lanczos_tridiag_pair(self, vin_a, vin_b, nlanc: int, threshold: float = 1e-12):
         """Two sp_lanc_tridiag runs (two Green's-function channels) on one product, real H: vin_a, vin_b = REAL start vectors in

@@ -118,18 +118,22 @@ def density_coefficients(kind, nimp: int) -> np.ndarray:
     return cf
 
 
-def susceptibility(sec, psi, e_state: float, kind, z, nlanc: int = 200, cutoff: float = 1e-8):
+def susceptibility(sec, psi, e_state: float, kind, z, nlanc: int = 200, cutoff: float = 1e-8, paired: bool = False):
     """chi_ab(z) = <<dO_a; dO_b>> of ONE device-resident eigenstate psi (energy e_state) of the open sector `sec`: the impurity spin
     ("spin": O_a = S^z_a) or charge ("charge": O_a = n_a) susceptibility between the impurity orbitals, or between the operators of an
     explicit coefficient array (nops, 2, Nimp); the reference's buildChi_impurity stage (ED_GREENS_FUNCTIONS.f90:68-106).  One
     apply_density_ops call builds every dO_a|psi>; column b is one lanczos_tridiag_probes run from dO_b|psi> with all dO_a|psi> as probes
     (a column whose start vector has norm2 < 1e-24 is zero and is skipped), then greens.poles_weights and greens.chi_evaluate.  Nothing
     Dim-sized crosses PCIe.  A thermal average is the caller's sum over the state list, sum_m peso_m chi^(m) (thermal_weights).
+    paired=True (real H only: sec.real_vectors_available, HxvError otherwise): the columns that are not skipped are taken two at a time
+    through lanczos_tridiag_pair_probes, one product per step for both; a column left without a partner runs singly.
     -> (chi[len(z), nops, nops] complex128, info = {"mean", "norm2", "nsteps", "dropped_weight"})."""
     from . import greens
 
     if not sec.nimp():
         raise HxvError("susceptibility needs a sector built from a model with Nimp <= 10")
+    if paired and not sec.real_vectors_available:
+        raise HxvError("susceptibility: paired=True needs a real Hamiltonian (real_vectors_available)")
     cf = density_coefficients(kind, sec.nimp())
     nops = cf.shape[0]
     if nops > 8:
@@ -138,11 +142,17 @@ def susceptibility(sec, psi, e_state: float, kind, z, nlanc: int = 200, cutoff: 
     vecs, mean, norm2 = sec.apply_density_ops(cf, psi, subtract_mean=True)
     chi = np.zeros((z.size, nops, nops), dtype=np.complex128)
     nsteps, dropped = np.zeros(nops, dtype=np.int64), 0.0
-    for b in range(nops):
-        if norm2[b] < 1e-24:
-            continue
-        al, bl, ov, n = sec.lanczos_tridiag_probes(vecs[b], vecs, min(int(nlanc), sec.Dim))
-        poles, wts = greens.poles_weights(al[:n], bl[:n], ov, np.sqrt(norm2[b]))
-        chi[:, :, b], d = greens.chi_evaluate(poles, wts, z, e_state, cutoff)
-        nsteps[b], dropped = n, dropped + d
+    nl = min(int(nlanc), sec.Dim)
+    cols = [b for b in range(nops) if not norm2[b] < 1e-24]
+    while cols:
+        if paired and len(cols) > 1:
+            pair, cols = cols[:2], cols[2:]
+            runs = sec.lanczos_tridiag_pair_probes(vecs[pair[0]], vecs[pair[1]], vecs, nl)
+        else:
+            pair, cols = cols[:1], cols[1:]
+            runs = (sec.lanczos_tridiag_probes(vecs[pair[0]], vecs, nl),)
+        for b, (al, bl, ov, n) in zip(pair, runs):
+            poles, wts = greens.poles_weights(al[:n], bl[:n], ov, np.sqrt(norm2[b]))
+            chi[:, :, b], d = greens.chi_evaluate(poles, wts, z, e_state, cutoff)
+            nsteps[b], dropped = n, dropped + d
     return chi, dict(mean=mean, norm2=norm2, nsteps=nsteps, dropped_weight=dropped)

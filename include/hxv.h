@@ -348,11 +348,37 @@ int hxv_lanczos_tridiag_pair_host(hxv_handle *h, const void *vin_a_host, const v
  * hands them, HXV_ERR_ARG or HXV_ERR_STATE depending on the transport): the driver clears that place.
  * Errors: HXV_ERR_ARG for a NULL handle, d_vin, alanc, blanc or nsteps, nlanc < 1, nprobes outside [0, HXV_MAX_PROBES], nprobes > 0 with a
  * NULL list, a NULL entry or NULL overlaps, a zero or non-finite start vector.
- * Not provided: two probe runs paired as Re / Im of one complex vector, a graph-captured form, a host-vector form.                      */
+ * Two probe runs on one product: hxv_lanczos_tridiag_pair_probes below.  Not provided: a graph-captured form, a host-vector form.       */
 #define HXV_MAX_PROBES 8
 int hxv_lanczos_tridiag_probes(hxv_handle *h, const void *d_vin, int32_t nprobes, const void *const *d_probes, int32_t nlanc, double *alanc,
                                double *blanc, double *overlaps /* [nlanc][nprobes] complex, interleaved, step-major */, double threshold,
                                int32_t *nsteps);
+/* TWO probe runs on one product, for real H: hxv_lanczos_tridiag_pair with the overlaps of hxv_lanczos_tridiag_probes for each component.  The
+ * runs of a Green's-function solve that share a probe list -- orbitals i, i' of one spin and sector with all c^dagger_j|gs> as probes, or two
+ * columns of a susceptibility with all dO_a|psi> -- pay for one product per step between them, and the probes are read once for both.
+ *   d_vin_a, d_vin_b, alanc_x, blanc_x, *nsteps_x, threshold : as in hxv_lanczos_tridiag_pair (the same driver: that entry is the nprobes = 0
+ *     form of this one, with the same bits); each component has its own scalars and breaks down on its own, the other one then goes on alone.
+ *   d_probes : nprobes vectors, 0 .. HXV_MAX_PROBES, in the complex layout like d_vin, shared by both components.  Their imaginary parts must be
+ *     exactly zero on all ranks, like the start vectors': ONE reduction checks all of them, every rank sees its sum, and all ranks return
+ *     HXV_ERR_ARG together when it is not zero (a complex probe goes through hxv_lanczos_tridiag_probes' complex path).  The probes' real parts
+ *     are written once into double buffers on the slab's own index, taken from the device-buffer cache and returned before the call returns.
+ *   overlaps_x[2*(k*nprobes + j)] = <p_j|q_k^x> for the UNIT Lanczos vector of component x and step k < *nsteps_x, [.. + 1] = 0 exactly: the
+ *     layout of hxv_lanczos_tridiag_probes' overlaps, so hxv_gf_from_probes takes each array as it is.  Entries of steps a component did not
+ *     run are zero.
+ * Per step one pass over the stored complex vector and the probes, before the product: 16 + 8*nprobes bytes per state for both components (two
+ * single real runs read 2*(8 + 8*nprobes)); no floating-point atomics.  Each component's alanc, blanc, nsteps and overlaps are bit-identical
+ * to hxv_lanczos_tridiag_probes on that start vector with the same probes through the complex-vector kernels (option real_vectors = 0, any
+ * job_up, lanczos_graph = 0); against its default real-vector path they agree to rounding, as for hxv_lanczos_tridiag_pair.
+ * "lanczos_real_last" reports 2.  Needs the fused recurrence (option "lanczos_fused" = 1).
+ * SPLIT SECTORS: as hxv_lanczos_tridiag_probes -- the 2*nprobes sums of a step in ONE all-reduce, start vectors at hxv_slab_home staged, a probe
+ * inside a gather buffer refused on all ranks together.
+ * Errors: HXV_ERR_UNSUPPORTED for a complex H or without the fused recurrence; HXV_ERR_ARG for a NULL handle, start vector, alanc or blanc,
+ * nlanc < 1, nprobes outside [0, HXV_MAX_PROBES], nprobes > 0 with a NULL list, a NULL entry or a NULL overlaps array, an imaginary part in a
+ * start vector or a probe, a zero or non-finite start vector.  Not provided: a graph-captured form, a host-vector form.                  */
+int hxv_lanczos_tridiag_pair_probes(hxv_handle *h, const void *d_vin_a, const void *d_vin_b, int32_t nprobes, const void *const *d_probes,
+                                    int32_t nlanc, double *alanc_a, double *blanc_a,
+                                    double *overlaps_a /* [nlanc][nprobes] complex, interleaved, step-major */, double *alanc_b,
+                                    double *blanc_b, double *overlaps_b, double threshold, int32_t *nsteps_a, int32_t *nsteps_b);
 /* From the overlaps to poles and weights (pure host code, no device):  T = Z diag(lambda) Z^T  of the nsteps x nsteps tridiagonal matrix
  * (alanc, blanc as returned above; the engine's own implicit QL, no LAPACK),
  *     poles[n] = lambda_n (ascending),   weights[2*(n*nprobes + j)], [.. + 1] = Re, Im of  norm * Z_{1n} * sum_k o_kj Z_kn,
