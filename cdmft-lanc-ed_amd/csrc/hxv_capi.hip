@@ -474,36 +474,10 @@ int hxv_apply_up_add(hxv_handle* h, const void* d_v_local, const void* d_w, void
 
 }  // extern "C"
 
-namespace hxv {
-namespace {
-// contiguous reference layout [ncols][dimup] -> device layout [ncols][pitch]: device row d holds reference row iperm[d], times the basis sign
-__global__ void __launch_bounds__(256) rows_ref_to_dev(const double2* __restrict__ src, double2* __restrict__ dst, const int32_t* __restrict__ iperm,
-                                                       const uint8_t* __restrict__ sign, int dimup, int pitch, int64_t n) {
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
-    const int64_t c = t / pitch;
-    const int d = (int)(t - c * pitch);
-    double2 x = make_double2(0.0, 0.0);   // (pad rows are zero in every device vector)
-    if (d < dimup) {
-      x = src[c * dimup + iperm[d]];
-      if (sign[d]) x = make_double2(-x.x, -x.y);
-    }
-    dst[t] = x;
-  }
-}
-// device layout -> contiguous reference layout: reference row i sits at device row perm[i]
-__global__ void __launch_bounds__(256) rows_dev_to_ref(const double2* __restrict__ src, double2* __restrict__ dst, const int32_t* __restrict__ perm,
-                                                       const uint8_t* __restrict__ sign, int dimup, int pitch, int64_t n) {
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
-    const int64_t c = t / dimup;
-    const int i = (int)(t - c * dimup);
-    const int d = perm[i];
-    double2 x = src[c * pitch + d];
-    if (sign[d]) x = make_double2(-x.x, -x.y);
-    dst[t] = x;
-  }
-}
-}  // namespace
+// rows_ref_to_dev and rows_dev_to_ref; included here, where their text stood, so that the file's device code keeps its order
+#include "hxv_rows_kernels.hpp"
 
+namespace hxv {
 int slab_from_host(hxv_handle* h, const void* v_host, double2* d_vec) {
   const SectorHost& s = h->host;
   const size_t col = (size_t)s.dimup * sizeof(double2), pit = (size_t)s.pitch * sizeof(double2);
