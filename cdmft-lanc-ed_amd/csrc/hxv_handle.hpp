@@ -113,6 +113,7 @@ struct TableArena {
 // same sector for every Green's-function channel (build_Hv_sector / delete_Hv_sector around each sp_lanc_tridiag, ED_GF_NORMAL.f90:208-222),
 // and the images of closed sectors stay in a per-process cache keyed by everything that determines them (hxv_capi.hip: sector_cache).
 struct PtTables;
+struct SpTables;
 struct SectorImage {
   SectorHost host;
   DevSector dev{};
@@ -143,6 +144,10 @@ struct SectorImage {
   struct DopTables;
   std::shared_ptr<DopTables> dop;
   std::mutex dop_mu;
+  // the per-orbital tables of hxv_apply_spin_pair INTO this sector (hxv_spin_pair.hip), one entry per (source sector and its row order,
+  // flags), most recently used last, a few at most
+  std::vector<std::shared_ptr<SpTables>> sp;
+  std::mutex sp_mu;
   ~SectorImage();
 };
 // the cache of closed sectors' images (hxv_cache.cpp); an empty key means "do not cache"

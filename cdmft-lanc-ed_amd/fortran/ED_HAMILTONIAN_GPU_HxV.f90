@@ -45,6 +45,7 @@ module ED_HAMILTONIAN_GPU_HXV
   !two probe runs on one product (real H; include/hxv.h: hxv_lanczos_tridiag_pair_probes)
   public :: gpu_sp_lanc_tridiag_pair_probes_dev
   public :: gpu_apply_density_ops_dev
+  public :: gpu_apply_spin_pair_dev
   public :: gpu_vector_to_host
   public :: gpu_vector_from_host
   public :: gpu_free_vector
@@ -399,6 +400,14 @@ module ED_HAMILTONIAN_GPU_HXV
        type(c_ptr),intent(in)    :: d_out(*)
        real(c_double)            :: mean(*),norm2(*)
      end function hxv_apply_density_ops
+     integer(c_int) function hxv_apply_spin_pair(from,to,create_up,create_dw,nterms,orb_up,orb_dw,coef,d_psi,d_out,norm2) bind(C,name="hxv_apply_spin_pair")
+       import :: c_int, c_int32_t, c_ptr, c_double
+       type(c_ptr),value             :: from,to,d_psi,d_out
+       integer(c_int32_t),value      :: create_up,create_dw,nterms
+       integer(c_int32_t),intent(in) :: orb_up(*),orb_dw(*)
+       real(c_double),intent(in)     :: coef(*)
+       real(c_double)                :: norm2
+     end function hxv_apply_spin_pair
   end interface
 
   type(c_ptr),save :: handle = c_null_ptr   !one open sector at a time (ED_HAMILTONIAN_COMMON.f90:17-18)
@@ -1011,6 +1020,43 @@ contains
     call check(hxv_apply_density_ops(handle,int(nops,c_int32_t),cf,sub,psi%d,olist,m,n2),"gpu_apply_density_ops_dev")
     mean=m(1:nops); norm2=n2(1:nops)
   end subroutine gpu_apply_density_ops_dev
+
+  !> Operators that change both spin sectors at once (include/hxv.h, hxv_apply_spin_pair): the start vectors of the pair susceptibility
+  !! (build_chi_pair, ED_GREENS_FUNCTIONS.f90:68-106) and of the transverse spin susceptibility,
+  !!     out = sum_t coef(t) X_t Y_t psi,   X_t = c^dagger (create_up) or c on up orbital ipos_up(t),   Y_t the same on dw orbital ipos_dw(t),
+  !! from psi's sector (kept open by gpu_keep_sector, as gpu_apply_ladder takes it) into the OPEN sector (nup+-1, ndw+-1); ipos = 1-based
+  !! orbital position in the spin string, iorb+(ilat-1)*Norb for the impurity; 1 to 32 terms, summed in the order given; norm2 = <out|out>.
+  !! The signs are those of two gpu_apply_ladder calls.  An empty out is allocated on the open sector.  chi_ab then takes, per operator, one
+  !! gpu_sp_lanc_tridiag_probes_dev run in each neighbouring sector and gpu_gf_from_probes with norm = sqrt(norm2) (INTEGRATION.md section 4).
+  !! Unsplit sectors only.
+  subroutine gpu_apply_spin_pair_dev(psi,ipos_up,ipos_dw,coef,create_up,create_dw,out,norm2)
+    type(gpu_vector),intent(in)    :: psi
+    integer,intent(in)             :: ipos_up(:),ipos_dw(:)
+    complex(8),intent(in)          :: coef(:)
+    logical,intent(in)             :: create_up,create_dw
+    type(gpu_vector),intent(inout) :: out
+    real(8),intent(out)            :: norm2
+    integer(c_int32_t)             :: ou(32),od(32),cu,cd
+    real(8)                        :: cf(64)
+    integer                        :: t,nterms
+    if(.not.c_associated(handle))stop "gpu_apply_spin_pair_dev ERROR: Hsector NOT set (build the target sector first)"
+    if(.not.vec_alive(psi))stop "gpu_apply_spin_pair_dev ERROR: empty source vector, or its sector was closed under it (gpu_keep_sector keeps it open)"
+    nterms=size(coef)
+    if(nterms<1.or.nterms>32)stop "gpu_apply_spin_pair_dev ERROR: 1 to 32 terms"
+    if(size(ipos_up)/=nterms.or.size(ipos_dw)/=nterms)stop "gpu_apply_spin_pair_dev ERROR: ipos_up, ipos_dw and coef have one entry per term"
+    if(.not.c_associated(out%d))then
+       call check(hxv_vector_alloc(handle,out%d),"gpu_apply_spin_pair_dev")
+       call vec_born(out,out%d,.false.)
+    endif
+    if(out%sector_id/=handle_serial)stop "gpu_apply_spin_pair_dev ERROR: the target vector does not belong to the open sector"
+    do t=1,nterms
+       ou(t)=int(ipos_up(t)-1,c_int32_t); od(t)=int(ipos_dw(t)-1,c_int32_t)
+       cf(2*t-1)=dble(coef(t)); cf(2*t)=aimag(coef(t))
+    enddo
+    cu=0; if(create_up)cu=1
+    cd=0; if(create_dw)cd=1
+    call check(hxv_apply_spin_pair(psi%sector,handle,cu,cd,int(nterms,c_int32_t),ou,od,cf,psi%d,out%d,norm2),"gpu_apply_spin_pair_dev")
+  end subroutine gpu_apply_spin_pair_dev
 
   !> the vector in the reference's host layout (this rank's slab), when it is wanted there after all (e.g. state_list of ED_DIAG)
   subroutine gpu_vector_to_host(vect,v)

@@ -50,7 +50,7 @@ EXPORTS = [
     "hxv_sector_cache_clear", "hxv_sector_cache_stats", "hxv_comm_abort", "hxv_comm_library", "hxv_comm_cache_stats", "hxv_comm_cache_clear", "hxv_host_register", "hxv_host_unregister",
     "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
     "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_reduced_dm_elems", "hxv_reduced_dm_accumulate", "hxv_twin_vector", "hxv_twin_split_plan",
-    "hxv_lanczos_tridiag_probes", "hxv_gf_from_probes", "hxv_apply_density_ops", "hxv_lanczos_tridiag_pair_probes",
+    "hxv_lanczos_tridiag_probes", "hxv_gf_from_probes", "hxv_apply_density_ops", "hxv_lanczos_tridiag_pair_probes", "hxv_apply_spin_pair",
 ]
 
 _lib = None
@@ -173,6 +173,7 @@ def load_library():
     L.hxv_lanczos_tridiag_pair_probes.argtypes = [vp, vp, vp, i32, C.POINTER(vp), i32, pd, pd, pd, pd, pd, pd, dbl, pi32, pi32]
     L.hxv_gf_from_probes.argtypes = [i32, pd, pd, i32, pd, dbl, pd, pd]
     L.hxv_apply_density_ops.argtypes = [vp, i32, pd, i32, vp, C.POINTER(vp), pd, pd]
+    L.hxv_apply_spin_pair.argtypes = [vp, vp, i32, i32, i32, pi32, pi32, pd, vp, vp, pd]
     _lib = L
     return L
 
@@ -1058,6 +1059,32 @@ class HxvSector:
         _chk(load_library().hxv_apply_density_ops(self._h, nops, _p(cf, C.c_double), int(bool(subtract_mean)), psi.data_ptr(), olist,
                                                   _p(mean, C.c_double), _p(norm2, C.c_double)), "hxv_apply_density_ops")
         return out, mean[:nops], norm2[:nops]
+
+    def apply_spin_pair(self, to: "HxvSector", terms, create_up: bool, create_dw: bool, psi, out=None):
+        """hxv_apply_spin_pair (include/hxv.h): out = sum_t coef_t X_t Y_t psi from this sector into `to` = (nup +- 1, ndw +- 1), X_t = c^dagger
+        (create_up) or c on orbital orb_up of spin up, Y_t the same on orb_dw of spin dw: the start vectors of the pair and spin-flip
+        susceptibilities (hxv.observables.spin_pair_susceptibility).  terms: a sequence of (orb_up, orb_dw, coef), 1 to 32 of them, summed in
+        the order given; the sign convention is that of two apply_ladder calls.  psi: a device vector of this sector in the padded layout
+        (localElems complex128 elements); out: one of `to`, allocated when not given; every element is written.  Unsplit sectors only.
+        -> (out, norm2 = <out|out>)."""
+        import torch
+
+        if not (torch.is_tensor(psi) and psi.is_cuda and psi.dtype == torch.complex128 and psi.is_contiguous() and psi.numel() == self.localElems):
+            raise HxvError(f"apply_spin_pair takes a device vector in the padded layout (complex128, localElems = {self.localElems} elements)")
+        terms = list(terms)
+        ou = np.ascontiguousarray([t[0] for t in terms], dtype=np.int32)
+        od = np.ascontiguousarray([t[1] for t in terms], dtype=np.int32)
+        cf = np.ascontiguousarray([complex(t[2]) for t in terms], dtype=np.complex128)
+        if out is None:
+            out = torch.empty(to.localElems, dtype=torch.complex128, device=psi.device)
+        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.complex128 and out.is_contiguous() and out.numel() == to.localElems):
+            raise HxvError("apply_spin_pair: out is a device vector of `to` in the padded layout")
+        torch.cuda.synchronize(psi.device)
+        n2 = C.c_double()
+        _chk(load_library().hxv_apply_spin_pair(self._h, to._h, int(bool(create_up)), int(bool(create_dw)), len(terms), _p(ou, C.c_int32), _p(od, C.c_int32),
+                                                C.cast(cf.ctypes.data, C.POINTER(C.c_double)), psi.data_ptr(), out.data_ptr(), C.byref(n2)),
+             "hxv_apply_spin_pair")
+        return out, n2.value
 
     def time_lanczos(self, nrep: int) -> float:
         import torch

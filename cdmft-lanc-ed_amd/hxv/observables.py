@@ -156,3 +156,63 @@ def susceptibility(sec, psi, e_state: float, kind, z, nlanc: int = 200, cutoff: 
             chi[:, :, b], d = greens.chi_evaluate(poles, wts, z, e_state, cutoff)
             nsteps[b], dropped = n, dropped + d
     return chi, dict(mean=mean, norm2=norm2, nsteps=nsteps, dropped_weight=dropped)
+
+
+def spin_pair_terms(kind, nimp: int):
+    """The operators of HxvSector.apply_spin_pair as a list of term lists [(orb_up, orb_dw, coef), ...], one per operator: "local_pair" =
+    c_{a,up} c_{a,dw} of every impurity orbital (flags create_up = create_dw = False), "spin_flip" = S^-_a = c^+_{a,dw} c_{a,up} (create_up =
+    False, create_dw = True); an explicit list of term lists is taken as it is."""
+    if isinstance(kind, str):
+        if kind not in ("local_pair", "spin_flip"):
+            raise HxvError('spin_pair_terms: kind is "local_pair", "spin_flip" or a list of term lists')
+        return [[(a, a, 1.0)] for a in range(nimp)]
+    return [[(int(i), int(j), complex(c)) for i, j, c in op] for op in kind]
+
+
+def spin_pair_susceptibility(sec, sec_lower, sec_raise, psi, e_state: float, ops, create_up: bool, create_dw: bool, z, nlanc: int = 200):
+    """chi_ab(z) = <<O_a; O_b^+>> of ONE device-resident eigenstate psi (energy e_state) of the open sector `sec` for operators that change
+    both spin sectors, O_a = sum_t coef_t X_t Y_t with the flags (create_up, create_dw) (HxvSector.apply_spin_pair; ops as spin_pair_terms
+    returns them, at most 8):
+
+        chi_ab(z) = -[ sum_n <O_a^+ psi|n><n|O_b^+ psi> / (z - e_n)  -  sum_m <O_b psi|m><m|O_a psi> / (z + e_m) ],   e = E_level - e_state,
+
+    n over `sec_raise`, the sector O^+ reaches (the flags inverted), m over `sec_lower`, the one O reaches; a sector that does not exist
+    (nup or ndw outside [0, Ns]) is passed as None and its sum is zero.  O^+ is the same term list with conjugated coefficients and both
+    flags inverted.  Column b of the first sum is one lanczos_tridiag_probes run in sec_raise from O_b^+ psi with all O_a^+ psi as probes,
+    row a of the second one run in sec_lower from O_a psi with all O_b psi as probes; a start vector with norm2 < 1e-24 is skipped.  For
+    Hermitian O this is chi_evaluate's formula.  Nothing Dim-sized crosses PCIe.
+    -> (chi[len(z), nops, nops] complex128, info = {"norm2_raise", "norm2_lower", "nsteps_raise", "nsteps_lower"})."""
+    from . import greens
+
+    ops = [list(op) for op in ops]
+    nops = len(ops)
+    if nops < 1 or nops > 8:
+        raise HxvError("spin_pair_susceptibility: 1 to 8 operators per call (HXV_MAX_PROBES)")
+    z = np.asarray(z, dtype=np.complex128).reshape(-1)
+    chi = np.zeros((z.size, nops, nops), dtype=np.complex128)
+    info = dict(norm2_raise=np.zeros(nops), norm2_lower=np.zeros(nops), nsteps_raise=np.zeros(nops, dtype=np.int64),
+                nsteps_lower=np.zeros(nops, dtype=np.int64))
+    if sec_raise is not None:
+        dag = [[(i, j, np.conj(complex(c))) for i, j, c in op] for op in ops]
+        vecs = [sec.apply_spin_pair(sec_raise, op, not create_up, not create_dw, psi) for op in dag]
+        nl = min(int(nlanc), sec_raise.Dim)
+        for b in range(nops):
+            info["norm2_raise"][b] = vecs[b][1]
+            if vecs[b][1] < 1e-24:
+                continue
+            al, bl, ov, n = sec_raise.lanczos_tridiag_probes(vecs[b][0], [v for v, _ in vecs], nl)
+            poles, wts = greens.poles_weights(al[:n], bl[:n], ov, np.sqrt(vecs[b][1]))
+            chi[:, :, b] -= greens.evaluate(poles, wts, z, e_state, +1.0)   # wts[n, a] = <O_a^+ psi|n><n|O_b^+ psi>
+            info["nsteps_raise"][b] = n
+    if sec_lower is not None:
+        vecs = [sec.apply_spin_pair(sec_lower, op, create_up, create_dw, psi) for op in ops]
+        nl = min(int(nlanc), sec_lower.Dim)
+        for a in range(nops):
+            info["norm2_lower"][a] = vecs[a][1]
+            if vecs[a][1] < 1e-24:
+                continue
+            al, bl, ov, n = sec_lower.lanczos_tridiag_probes(vecs[a][0], [v for v, _ in vecs], nl)
+            poles, wts = greens.poles_weights(al[:n], bl[:n], ov, np.sqrt(vecs[a][1]))
+            chi[:, a, :] += greens.evaluate(poles, wts, z, e_state, -1.0)   # wts[m, b] = <O_b psi|m><m|O_a psi>
+            info["nsteps_lower"][a] = n
+    return chi, info

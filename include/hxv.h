@@ -600,6 +600,40 @@ int hxv_apply_density_ops(hxv_handle *h, int32_t nops, const double *coef /* [no
                           int32_t subtract_mean, const void *d_psi, void *const *d_out /* nops device vectors of h */,
                           double *mean /* [nops] */, double *norm2 /* [nops] */);
 
+/* ---- operators that change both spin sectors at once: the start vectors of the pair and spin-flip susceptibilities ---------------
+ * The third susceptibility of the reference's two-particle stage (build_chi_pair, ED_GREENS_FUNCTIONS.f90:68-106, carried commented out)
+ * and the transverse spin susceptibility <<S^-;S^+>> start from O|psi> with
+ *     d_out = sum_t coef_t X_t Y_t d_psi,   X_t = c^dagger (create_up = 1) or c (0) on orbital orb_up[t] of spin up,
+ *                                           Y_t = c^dagger (create_dw = 1) or c (0) on orbital orb_dw[t] of spin dw,
+ * the two flags the same for all terms: c_{i,up} c_{j,dw} reaches (nup-1, ndw-1), c^+_{j,dw} c_{i,up} reaches (nup-1, ndw+1).  Orbitals are
+ * 0-based in [0, Ns) as in hxv_apply_ladder (bath orbitals included); `to` is the sector (nup +- 1, ndw +- 1) the flags name, same Ns, same
+ * device.  The terms are summed in the order given; a repeated (i, j) pair is allowed.  *norm2 = <out|out>; norm2 may be NULL.
+ * SIGN CONVENTION: that of two successive hxv_apply_ladder calls, each with its same-spin sign (-1)^(occupied orbitals of the SAME spin
+ * below the orbital) and no cross-spin sign; under it X_t and Y_t commute, and a single term with coef = 1 equals either order of the two
+ * ladder calls through the intermediate sector bit for bit (an element no term reaches is +0 here; the second ladder call may leave -0 there,
+ * differently in its two orders).  This differs from the true fermionic product by ONE constant +-1 per pair of
+ * sectors ((-1)^nup for an operator that moves a dw particle past all the up ones), which cancels in every <psi|O_a ... O_b^+|psi>.
+ * LAYOUT: d_psi is a vector of `from`, d_out one of `to`, both in the padded device layout; pad rows of d_psi are never read, every element
+ * of d_out is written, pad rows as exact zeros; d_out != d_psi.  DEVICE ROW ORDER: the row changes anyway, so each side's own order and
+ * basis signs apply and -- unlike a spin-dw ladder -- the two sectors need not share an order: the result equals hxv_vector_to_host / host
+ * arithmetic / hxv_vector_from_host whether none, one or both sectors have an order.
+ * One gather pass over the target: a thread owns elements of one target column, so the source column of a term is uniform over a workgroup
+ * and a term that does not reach the column is skipped for all of it; every distinct up orbital is looked up once per row for all the terms
+ * that use it; one 16-byte store per element; <out|out> from per-workgroup partial sums added in a fixed order.  A real d_psi with real
+ * coefficients gives imaginary parts that are exactly zero.  No floating-point atomics: the same inputs on the same handles give the same
+ * bits on every call.  The tables -- per distinct up orbital: target device row -> source device row and sign; per distinct dw orbital:
+ * target column -> source column and sign -- are built on first use and kept with `to`'s sector image, by source sector, flags and orbital.
+ * Runs on `to`'s stream and returns when norm2 is on the host.
+ * SPLIT SECTORS ARE NOT BUILT: HXV_ERR_UNSUPPORTED when either handle has nranks > 1, decided locally and identically on every rank before
+ * any collective step.
+ * Errors (nothing is written): HXV_ERR_ARG for a NULL handle, vector or term array, nterms outside [1, HXV_MAX_SPIN_PAIR_TERMS], an orbital
+ * outside [0, Ns), a coefficient that is not finite, d_out == d_psi, handles on different devices or with different Ns, `to` not the sector
+ * the flags name; HXV_ERR_STATE for handles without basis maps (from CSR, dw panels); HXV_ERR_UNSUPPORTED as above.                    */
+#define HXV_MAX_SPIN_PAIR_TERMS 32
+int hxv_apply_spin_pair(hxv_handle *from, hxv_handle *to, int32_t create_up, int32_t create_dw, int32_t nterms, const int32_t *orb_up,
+                        const int32_t *orb_dw, const double *coef /* [nterms] complex, interleaved */, const void *d_psi, void *d_out,
+                        double *norm2);
+
 /* ---- device vectors owned by the library --------------------------------------------------------------------------------
  * For host programs without a HIP binding of their own (the Fortran glue): a local vector of the handle's sector in the padded device
  * layout (hxv_localvec_elems() complex elements, zeroed), from the engine's buffer cache.  Such a pointer is what the device drivers take
