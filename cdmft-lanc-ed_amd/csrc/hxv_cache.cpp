@@ -18,7 +18,7 @@
 
 namespace hxv {
 
-SectorImage::~SectorImage() {
+void free_on_device(int device, const std::vector<void*>& allocs) {
   if (allocs.empty()) return;
   int cur = -1;
   (void)hipGetDevice(&cur);
@@ -26,6 +26,13 @@ SectorImage::~SectorImage() {
   for (void* p : allocs) (void)hipFree(p);
   if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
 }
+
+DeviceTables::~DeviceTables() {
+  if (base) more.push_back(base);
+  free_on_device(device, more);
+}
+
+SectorImage::~SectorImage() { free_on_device(device, allocs); }
 
 namespace {
 struct Cache {

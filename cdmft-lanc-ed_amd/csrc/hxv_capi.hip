@@ -13,7 +13,7 @@
 
 using namespace hxv;
 
-#include "hxv_handle.hpp"
+#include "hxv_call_scope.hpp"
 
 namespace hxv {
 namespace {
@@ -487,8 +487,9 @@ int slab_from_host(hxv_handle* h, const void* v_host, double2* d_vec) {
     if (pit > col) HIPCHK(hipMemset2DAsync(d_vec + s.dimup, pit, 0, pit - col, (size_t)s.qdw, h->stream));  // (pad rows are zero in every device vector)
     HIPCHK(hipStreamSynchronize(h->stream));
   } else {
+    CallScope scratch(h);
     double2* tmp = nullptr;
-    HIPCHK(pool_alloc(h->device, col * (size_t)s.qdw, (void**)&tmp));
+    HIPCHK(scratch.take(col * (size_t)s.qdw, &tmp));
     hipError_t e = hipMemcpyAsync(tmp, v_host, col * (size_t)s.qdw, hipMemcpyHostToDevice, h->stream);
     const int64_t n = (int64_t)s.pitch * s.qdw;
     if (e == hipSuccess) {
@@ -497,7 +498,6 @@ int slab_from_host(hxv_handle* h, const void* v_host, double2* d_vec) {
       e = hipGetLastError();
     }
     const hipError_t e2 = hipStreamSynchronize(h->stream);
-    pool_free(h->device, tmp);
     if (e != hipSuccess || e2 != hipSuccess) return fail(HXV_ERR_HIP, std::string("host -> device vector: ") + hipGetErrorString(e != hipSuccess ? e : e2));
   }
   h->h2d_bytes += (int64_t)(col * s.qdw);
@@ -512,15 +512,15 @@ int slab_to_host(hxv_handle* h, const double2* d_vec, void* v_host) {
     HIPCHK(hipMemcpy2DAsync(v_host, col, d_vec, pit, col, (size_t)s.qdw, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   } else {
+    CallScope scratch(h);
     double2* tmp = nullptr;
-    HIPCHK(pool_alloc(h->device, col * (size_t)s.qdw, (void**)&tmp));
+    HIPCHK(scratch.take(col * (size_t)s.qdw, &tmp));
     const int64_t n = (int64_t)s.dimup * s.qdw;
     hipLaunchKernelGGL(rows_dev_to_ref, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65536)), dim3(256), 0, h->stream, d_vec, tmp, h->dev.up_perm,
                        h->dev.up_sign, s.dimup, s.pitch, n);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(v_host, tmp, col * (size_t)s.qdw, hipMemcpyDeviceToHost, h->stream);
     const hipError_t e2 = hipStreamSynchronize(h->stream);
-    pool_free(h->device, tmp);
     if (e != hipSuccess || e2 != hipSuccess) return fail(HXV_ERR_HIP, std::string("device -> host vector: ") + hipGetErrorString(e != hipSuccess ? e : e2));
   }
   h->d2h_bytes += (int64_t)(col * s.qdw);
@@ -847,6 +847,7 @@ int64_t hxv_get_option(const hxv_handle* h, const char* name) {
   if (!strcmp(name, "lanczos_real_last")) return h->last_real;
   if (!strcmp(name, "pass_b_order_last")) return h->plan.dw_order_last;  // phase order the last pass-B launch ran (0 / 1; -1: none yet)
   if (!strcmp(name, "allreduce_count")) return h->n_allreduce;  // sum all-reduces of a split sector since creation (the drivers' dot products)
+  if (!strcmp(name, "pool_live_blocks")) return pool_live_blocks(h->device);  // buffer-cache blocks out on the handle's device (every handle's and call's)
   if (!strcmp(name, "slab_copies")) return h->n_slab_copy;  // exchanges whose vector was not at home in a gather buffer
   if (!strcmp(name, "lanczos_inplace")) return h->lz_inplace;
   if (!strcmp(name, "exchange_overlap")) return h->a2a_overlap;

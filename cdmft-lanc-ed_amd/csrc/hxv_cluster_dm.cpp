@@ -33,17 +33,12 @@ int hxv_cluster_dm_accumulate(hxv_handle* h, const void* d_psi, double weight, i
   if (nimp > CDM_MAX_NIMP) return fail(HXV_ERR_UNSUPPORTED, "hxv_cluster_dm_accumulate: Nimp > 5 (a dense matrix of 268 MB and more)");
   if (s.nranks > 1 && !comm_ready(h)) return fail(HXV_ERR_STATE, "hxv_cluster_dm_accumulate on a split sector needs the communicator (hxv_comm_init after opening it)");
   HIPCHK(hipSetDevice(h->device));
-  int rc_local = HXV_OK;
   std::shared_ptr<PtTables> t;
-  {
-    std::lock_guard<std::mutex> lk(h->img->cdm_mu);
-    if (!h->img->cdm) {
-      PtGroups up, dw;
-      const std::string err = cluster_dm_groups(s, nimp, up, dw);
-      rc_local = err.empty() ? pt_make_tables(h, nimp, up, dw, 0, "cluster density matrix", h->img->cdm) : fail(HXV_ERR_STATE, err);
-    }
-    t = h->img->cdm;
-  }
+  const int rc_local = pt_stored_tables(h, "cluster density matrix", "", 1, t, [&](std::shared_ptr<PtTables>& nt) {
+    PtGroups up, dw;
+    const std::string err = cluster_dm_groups(s, nimp, up, dw);
+    return err.empty() ? pt_make_tables(h, nimp, up, dw, 0, "cluster density matrix", nt) : fail(HXV_ERR_STATE, err);
+  });
   return pt_accumulate(h, t, rc_local, d_psi, weight, accumulate != 0, cdm, "hxv_cluster_dm_accumulate");
 }
 

@@ -21,32 +21,17 @@
 #include <algorithm>
 #include <cmath>
 
-#include "hxv_handle.hpp"
+#include "hxv_call_scope.hpp"
 
 using namespace hxv;
 
-namespace hxv {
-struct SectorImage::DopTables {
+namespace {
+struct DopTables : DeviceTables {
   uint32_t *occ_up = nullptr, *occ_dw = nullptr;  // [pitch] by device row (pad rows 0), [max(qdw,1)] by local column
   int nchunk = 1, rows = 0;                       // chunks a column is cut into, rows of a chunk (a multiple of 8)
   int64_t nitems = 0;
   int grid = 1;                                   // workgroups of the two passes
-  void* base = nullptr;
-  int device = -1;
-  int64_t bytes = 0;
-  ~DopTables() {
-    if (!base) return;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(device);
-    (void)hipFree(base);
-    if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
-  }
 };
-}  // namespace hxv
-
-namespace {
-using DopTables = SectorImage::DopTables;
 constexpr int DOP_THREADS = 256;
 constexpr int DOP_WAVES = DOP_THREADS / 64;
 constexpr int DOP_MAX = HXV_MAX_DENSITY_OPS;
@@ -264,41 +249,24 @@ int hxv_apply_density_ops(hxv_handle* h, int32_t nops, const double* coef, int32
   };
   int rc_local = check_args();
   std::shared_ptr<DopTables> t;
-  if (rc_local == HXV_OK) {
-    std::lock_guard<std::mutex> lk(h->img->dop_mu);
-    if (!h->img->dop) {
-      int ncu = 0;
-      if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || ncu < 1) ncu = 256;
-      auto nt = std::make_shared<DopTables>();
-      const std::string err = build_tables(s, nimp, h->device, ncu, *nt);
-      if (err.empty())
-        h->img->dop = nt;
-      else
-        rc_local = fail(err.rfind("density operators tables", 0) == 0 ? HXV_ERR_HIP : HXV_ERR_STATE, err);
-    }
-    t = h->img->dop;
-  }
+  if (rc_local == HXV_OK)
+    rc_local = h->img->tables.get("density operators", "", 1, t, [&](std::shared_ptr<DopTables>& nt) {
+      nt = std::make_shared<DopTables>();
+      const std::string err = build_tables(s, nimp, h->device, compute_units(h->device), *nt);
+      return err.empty() ? HXV_OK : fail(err.rfind("density operators tables", 0) == 0 ? HXV_ERR_HIP : HXV_ERR_STATE, err);
+    });
   // scratch: the coefficients, the workgroups' partial sums, the sums of pass 1 (nops + 1) and of pass 2 (nops)
   const size_t ncoef = (size_t)DOP_MAX * 2 * DOP_MAX_NIMP;
   double* d_ws = nullptr;
-  if (rc_local == HXV_OK && pool_alloc(h->device, (ncoef + (size_t)t->grid * DOP_NSUM + 2 * DOP_NSUM) * sizeof(double), (void**)&d_ws) != hipSuccess) {
-    d_ws = nullptr;
+  CallScope scratch(h);
+  if (rc_local == HXV_OK && scratch.take((ncoef + (size_t)t->grid * DOP_NSUM + 2 * DOP_NSUM) * sizeof(double), &d_ws) != hipSuccess)
     rc_local = fail(HXV_ERR_HIP, "hxv_apply_density_ops: scratch buffer");
-  }
-  auto release = [&]() {
-    (void)hipStreamSynchronize(st);
-    if (d_ws) pool_free(h->device, d_ws);
-  };
   int rc = split ? comm_agree(h, rc_local) : rc_local;
-  if (rc) {
-    release();
-    return rc;
-  }
+  if (rc) return rc;
   double *d_coef = d_ws, *d_part = d_ws + ncoef, *d_s1 = d_part + (size_t)t->grid * DOP_NSUM, *d_s2 = d_s1 + DOP_NSUM;
   const DopShape shape{s.dimup, s.pitch, s.qdw, nimp, nops, t->nchunk, t->rows, t->nitems};
   const double2* psi = (const double2*)d_psi;
   auto step_failed = [&](const char* what, hipError_t e) {
-    release();
     return fail(HXV_ERR_HIP, std::string("hxv_apply_density_ops: ") + what + ": " + hipGetErrorString(e));
   };
   hipError_t e = hipMemcpyAsync(d_coef, coef, (size_t)nops * 2 * nimp * sizeof(double), hipMemcpyHostToDevice, st);
@@ -310,20 +278,14 @@ int hxv_apply_density_ops(hxv_handle* h, int32_t nops, const double* coef, int32
   if (e != hipSuccess) return step_failed("pass 1", e);
   if (split) {
     rc = comm_allreduce_sum(h, d_s1, (size_t)nops + 1, st);
-    if (rc) {
-      release();
-      return rc;
-    }
+    if (rc) return rc;
   }
   double s1[DOP_NSUM] = {}, s2[DOP_NSUM] = {};
   e = hipMemcpyAsync(s1, d_s1, ((size_t)nops + 1) * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return step_failed("sums of pass 1", e);
   // the global <psi|psi>: the same number on every rank, so every rank takes the same way out
-  if (!(s1[nops] > 0.0) || !std::isfinite(s1[nops])) {
-    release();
-    return fail(HXV_ERR_ARG, "hxv_apply_density_ops: the state is zero or not finite");
-  }
+  if (!(s1[nops] > 0.0) || !std::isfinite(s1[nops])) return fail(HXV_ERR_ARG, "hxv_apply_density_ops: the state is zero or not finite");
   DopOut out{};
   double m[DOP_MAX] = {};
   for (int a = 0; a < nops; ++a) {
@@ -338,15 +300,11 @@ int hxv_apply_density_ops(hxv_handle* h, int32_t nops, const double* coef, int32
   if (e != hipSuccess) return step_failed("pass 2", e);
   if (split) {
     rc = comm_allreduce_sum(h, d_s2, (size_t)nops, st);
-    if (rc) {
-      release();
-      return rc;
-    }
+    if (rc) return rc;
   }
   e = hipMemcpyAsync(s2, d_s2, (size_t)nops * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return step_failed("sums of pass 2", e);
-  release();
   for (int a = 0; a < nops; ++a) {
     mean[a] = m[a];
     norm2[a] = s2[a];

@@ -19,7 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "hxv_handle.hpp"
+#include "hxv_call_scope.hpp"
 #include "hxv_eigh_kernels.hpp"  // the streaming kernels and the two rotation launchers (also built alone by tests/device/eigh_kernels_check.hip)
 #include "hxv_eigh_host.hpp"     // jacobi_eigh, keep_count (also built alone by tests/host/eigh_small_check.cpp)
 
@@ -29,17 +29,6 @@ namespace {
 
 constexpr double DGKS_ETA2 = 0.01;  // refine when |w_after|^2 < eta^2 |w_before|^2
 constexpr double GS_TAU = 1e-13;     // projections below tau*|w| are measured but not subtracted (see gs_pass)
-
-struct DevFree {  // small buffers: hipFree; `pooled`: vector-sized ones, back to the engine's cache (hxv_pool.cpp)
-  std::vector<void*> p, pooled;
-  int device = 0;
-  ~DevFree() {
-    if (!pooled.empty()) (void)hipDeviceSynchronize();  // nothing may still be using a block that the next handle gets
-    for (void* q : pooled) pool_free(device, q);
-    for (void* q : p)
-      if (q) (void)hipFree(q);
-  }
-};
 
 }  // namespace
 
@@ -88,32 +77,26 @@ int hxv_eigh_lowest(hxv_handle* h, int32_t neigen, int32_t ncv, int32_t maxresta
                                      " but only " + std::to_string(free_b >> 20) + " MiB are free: lower ncv or use hxv_lanczos_eigh (3 vectors)");
   short_rc = comm_agree(h, short_rc);
   if (short_rc) return short_rc;
-  DevFree mem;
+  // The basis and the small arrays belong to the call's scope.  Its release synchronises the handle's stream, not the device: every product
+  // here goes through apply_slab, which joins the second stream of exchange_overlap back into the handle's stream by an event before it
+  // returns (hxv_exchange.cpp), so nothing of this call runs anywhere else when that stream has drained -- the Lanczos drivers return their
+  // blocks the same way.
+  CallScope mem(h);
   double2* V = nullptr;
   double *d_part = nullptr, *d_coef = nullptr, *d_S = nullptr;
-  mem.device = h->device;
   {
-    hipError_t ea = pool_alloc(h->device, need, (void**)&V);
+    hipError_t ea = mem.take(need, &V);
     int rca = comm_agree(h, ea == hipSuccess ? HXV_OK : fail(HXV_ERR_HIP, std::string("hxv_eigh_lowest: Krylov basis allocation: ") + hipGetErrorString(ea)));
-    if (rca) {
-      if (ea == hipSuccess) pool_free(h->device, V);
-      return rca;
-    }
+    if (rca) return rca;
   }
-  mem.pooled.push_back(V);
   HIPCHK(hipMemsetAsync(V, 0, need, h->stream));  // pad rows must be zero: the products never write them, the dots read them
-  HIPCHK(hipMalloc((void**)&d_part, (size_t)TR_BLOCKS * (2 * FUSE_NJ + 1) * sizeof(double)));  // ([blocks][2*JB] of tr_mdot or [blocks][2*FUSE_NJ] of the fused kernels, + [blocks] norms)
-  mem.p.push_back(d_part);
-  HIPCHK(hipMalloc((void**)&d_coef, (size_t)(2 * (MAXCV + 1) + 2) * sizeof(double)));
-  mem.p.push_back(d_coef);
-  HIPCHK(hipMalloc((void**)&d_S, (size_t)MAXCV * MAXCV * sizeof(double)));
-  mem.p.push_back(d_S);
+  HIPCHK(mem.take_device((size_t)TR_BLOCKS * (2 * FUSE_NJ + 1) * sizeof(double), &d_part));  // ([blocks][2*JB] of tr_mdot or [blocks][2*FUSE_NJ] of the fused kernels, + [blocks] norms)
+  HIPCHK(mem.take_device((size_t)(2 * (MAXCV + 1) + 2) * sizeof(double), &d_coef));
+  HIPCHK(mem.take_device((size_t)MAXCV * MAXCV * sizeof(double), &d_S));
   double* d_csel = nullptr;
   int* d_isel = nullptr;
-  HIPCHK(hipMalloc((void**)&d_csel, (size_t)2 * (MAXCV + 1) * sizeof(double)));
-  mem.p.push_back(d_csel);
-  HIPCHK(hipMalloc((void**)&d_isel, (size_t)(MAXCV + 1) * sizeof(int)));
-  mem.p.push_back(d_isel);
+  HIPCHK(mem.take_device((size_t)2 * (MAXCV + 1) * sizeof(double), &d_csel));
+  HIPCHK(mem.take_device((size_t)(MAXCV + 1) * sizeof(int), &d_isel));
   double* d_npart = d_part + (size_t)TR_BLOCKS * 2 * FUSE_NJ;
   double* d_nrm = d_coef + 2 * (MAXCV + 1);
   hipStream_t st = h->stream;
@@ -663,11 +646,9 @@ int hxv_eigh_lowest_host(hxv_handle* h, int32_t neigen, int32_t ncv, int32_t max
   HIPCHK(hipSetDevice(h->device));
   const int64_t n = (int64_t)h->host.pitch * h->host.qdw;
   const int64_t vecdim = (int64_t)h->host.dimup * h->host.qdw;  // eig_basis(vecDim, Neigen): this rank's slab of every vector
-  DevFree mem;
+  CallScope mem(h);
   double2* d = nullptr;
-  mem.device = h->device;
-  HIPCHK(pool_alloc(h->device, (size_t)neigen * n * sizeof(double2), (void**)&d));
-  mem.pooled.push_back(d);
+  HIPCHK(mem.take((size_t)neigen * n * sizeof(double2), &d));
   int rc = hxv_eigh_lowest(h, neigen, ncv, maxrestart, tol, evals, d, nconv_out, nmatvec_out);
   if (rc) return rc;
   // eig_basis(vecDim, Neigen) in the reference's layout: columns unpadded, eigenvectors consecutive (ED_DIAG.f90:145)

@@ -33,6 +33,7 @@ enum LzSlot : int {
 // vector-sized device buffers go through the engine's cache (hxv_pool.cpp): a fresh hipMalloc costs ~25 ms per GB here
 hipError_t pool_alloc(int device, size_t bytes, void** out);
 void pool_free(int device, void* ptr);
+int64_t pool_live_blocks(int device);        // blocks handed out on the device and not yet returned (get_option "pool_live_blocks")
 int ensure_wt(hxv_handle* h);                // (re)allocates the dw-hop scratch of the tiled kernels (hxv_capi.hip)
 // the two rank transports of a split sector and the collectives over them (hxv_transport.cpp)
 bool comm_ready(const hxv_handle* h);
@@ -108,12 +109,64 @@ struct TableArena {
   }
 };
 
+// hipFree of device allocations that belong to `device`, whatever the caller's current device is, which is restored (hxv_cache.cpp).  An
+// empty list calls nothing of the HIP runtime.
+void free_on_device(int device, const std::vector<void*>& allocs);
+inline int compute_units(int device) {  // what the drivers cut their work lists for; 256 where the runtime does not say
+  int ncu = 0;
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu < 1) ncu = 256;
+  return ncu;
+}
+// Device tables a driver derives from a sector image and keeps with it (TableStore below): `base` is what TableArena::commit returned, `more`
+// further allocations of a set that is filled piece by piece.  The destructor frees them on their device.
+struct DeviceTables {
+  void* base = nullptr;
+  std::vector<void*> more;
+  int device = -1;
+  int64_t bytes = 0;
+  DeviceTables() = default;
+  DeviceTables(const DeviceTables&) = delete;
+  DeviceTables& operator=(const DeviceTables&) = delete;
+  virtual ~DeviceTables();
+};
+// The table sets of one sector image, by driver family ("observables", "spin pair", ...) and key, most recently used last within a family.
+// Outside the sector cache's byte budget.  A driver reaches its tables through get() alone; adding a driver adds nothing here.
+struct TableStore {
+  struct Entry {
+    std::string family, key;
+    std::shared_ptr<DeviceTables> tables;
+  };
+  std::mutex mu;
+  std::vector<Entry> entries;
+  // out = the tables of (family, key): the stored ones, or what build(out) makes now -- a builder that fails (non-zero) stores nothing, the
+  // next call builds again --, after which the family keeps its `cap` most recently used sets (a call under way keeps a dropped set alive
+  // through its own reference).  Then ensure(*out), for sets that are completed on demand.  All of it under the store's lock: a table set
+  // is built once per image.  -> what build or ensure returned.
+  template <typename T, typename Build, typename Ensure>
+  int get(const char* family, const std::string& key, size_t cap, std::shared_ptr<T>& out, Build build, Ensure ensure) {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = std::find_if(entries.begin(), entries.end(), [&](const Entry& e) { return e.family == family && e.key == key; });
+    if (it != entries.end()) {
+      std::rotate(it, it + 1, entries.end());
+    } else {
+      std::shared_ptr<T> made;
+      if (int rc = build(made)) return rc;
+      const auto same = [&](const Entry& e) { return e.family == family; };
+      if ((size_t)std::count_if(entries.begin(), entries.end(), same) >= cap) entries.erase(std::find_if(entries.begin(), entries.end(), same));
+      entries.push_back({family, key, made});
+    }
+    out = std::static_pointer_cast<T>(entries.back().tables);
+    return ensure(*out);
+  }
+  template <typename T, typename Build>
+  int get(const char* family, const std::string& key, size_t cap, std::shared_ptr<T>& out, Build build) {
+    return get(family, key, cap, out, build, [](T&) { return 0; });
+  }
+};
 // What opening a sector builds and never changes afterwards: the host description (basis maps, one-spin matrices, diagonal tables),
 // the tile plan of the default options and every device table of both.  Handles SHARE it (shared_ptr): the reference re-opens the
 // same sector for every Green's-function channel (build_Hv_sector / delete_Hv_sector around each sp_lanc_tridiag, ED_GF_NORMAL.f90:208-222),
 // and the images of closed sectors stay in a per-process cache keyed by everything that determines them (hxv_capi.hip: sector_cache).
-struct PtTables;
-struct SpTables;
 struct SectorImage {
   SectorHost host;
   DevSector dev{};
@@ -129,25 +182,8 @@ struct SectorImage {
   // tables and the device pointers they will be patched into
   struct Pending;
   std::shared_ptr<Pending> pending;
-  // the pair and bin tables of the impurity observables (hxv_observables.hip), built on the first hxv_observables_accumulate
-  struct ObsTables;
-  std::shared_ptr<ObsTables> obs;
-  std::mutex obs_mu;
-  // the partial-trace tables (hxv_partial_trace.hip) of the cluster density matrix, built on the first hxv_cluster_dm_accumulate
-  std::shared_ptr<PtTables> cdm;
-  std::mutex cdm_mu;
-  // those of the subset density matrices (hxv_reduced_dm.cpp), one per (orbital mask, sign convention) asked for, most recently used last, a
-  // few at most; built by hxv_reduced_dm_accumulate
-  std::vector<std::pair<uint64_t, std::shared_ptr<PtTables>>> rdm;
-  std::mutex rdm_mu;
-  // the impurity-occupation words of the density-type operators (hxv_density_ops.hip), built on the first hxv_apply_density_ops
-  struct DopTables;
-  std::shared_ptr<DopTables> dop;
-  std::mutex dop_mu;
-  // the per-orbital tables of hxv_apply_spin_pair INTO this sector (hxv_spin_pair.hip), one entry per (source sector and its row order,
-  // flags), most recently used last, a few at most
-  std::vector<std::shared_ptr<SpTables>> sp;
-  std::mutex sp_mu;
+  // what the drivers derive from this image on first use: observables, density matrices, density operators, spin pair INTO this sector
+  TableStore tables;
   ~SectorImage();
 };
 // the cache of closed sectors' images (hxv_cache.cpp); an empty key means "do not cache"

@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "hxv_device.hpp"
-#include "hxv_handle.hpp"
+#include "hxv_call_scope.hpp"
 #include "hxv_ladder_kernels.hpp"
 
 using namespace hxv;
@@ -114,21 +114,13 @@ int hxv_apply_ladder_axpy(hxv_handle* from, hxv_handle* to, int32_t orbital, int
     int32_t* d_lists = nullptr;
     const size_t nl = send_cols.size() + 2 * (size_t)std::max(b.qdw, 1);
     int rc_local = HXV_OK;
-    hipError_t e1 = pool_alloc(to->device, std::max<size_t>(send_cols.size(), 1) * cb, (void**)&d_sendbuf);
-    hipError_t e2 = pool_alloc(to->device, std::max<size_t>((size_t)nrecv, 1) * cb, (void**)&d_recvbuf);
-    hipError_t e3 = hipMalloc((void**)&d_lists, std::max<size_t>(nl, 1) * sizeof(int32_t));
+    CallScope scratch(to);  // (its release synchronises the stream: the host lists above are read by asynchronous copies and outlive it)
+    hipError_t e1 = scratch.take(std::max<size_t>(send_cols.size(), 1) * cb, &d_sendbuf);
+    hipError_t e2 = scratch.take(std::max<size_t>((size_t)nrecv, 1) * cb, &d_recvbuf);
+    hipError_t e3 = scratch.take_device(std::max<size_t>(nl, 1) * sizeof(int32_t), &d_lists);
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) rc_local = fail(HXV_ERR_HIP, "hxv_apply_ladder: staging buffers for the column exchange");
-    auto release = [&]() {
-      (void)hipStreamSynchronize(st);
-      if (d_sendbuf) pool_free(to->device, d_sendbuf);
-      if (d_recvbuf) pool_free(to->device, d_recvbuf);
-      if (d_lists) (void)hipFree(d_lists);
-    };
     int rc = comm_agree(to, rc_local);
-    if (rc) {
-      release();
-      return rc;
-    }
+    if (rc) return rc;
     int32_t* d_send_cols = d_lists;
     int32_t* d_slot = d_lists + send_cols.size();
     int32_t* d_sgn = d_slot + std::max(b.qdw, 1);
@@ -137,19 +129,12 @@ int hxv_apply_ladder_axpy(hxv_handle* from, hxv_handle* to, int32_t orbital, int
     if (e == hipSuccess) e = hipMemcpyAsync(d_slot, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_sgn, sgn.data(), sgn.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = launch_pack_columns((const double2*)d_psi, d_sendbuf, d_send_cols, (int)send_cols.size(), a.pitch, st);
-    if (e != hipSuccess) {
-      release();
-      return fail(HXV_ERR_HIP, std::string("hxv_apply_ladder: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string("hxv_apply_ladder: ") + hipGetErrorString(e));
     rc = comm_sendrecv_cols(to, d_sendbuf, send_ptr.data(), d_recvbuf, recv_ptr.data(), cb, st);
-    if (rc) {
-      release();
-      return rc;
-    }
+    if (rc) return rc;
     if (b.qdw > 0)
       hipLaunchKernelGGL(ladder_cols_kernel, dim3((unsigned)b.qdw), dim3(256), 0, st, b.dimup, b.qdw, a.pitch, b.pitch, d_slot, d_sgn, (const double2*)d_psi,
                          d_recvbuf, (double2*)d_out, coef, accumulate ? 1 : 0);
-    release();  // (synchronises the stream: the host lists above are read by asynchronous copies)
   }
   if (norm2) {
     // <out|out> over ALL ranks of a split sector (pads of d_out must be zero: hxv.h)

@@ -8,7 +8,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "hxv_handle.hpp"
+#include "hxv_call_scope.hpp"
 #include "hxv_lanczos_host.hpp"
 #include "hxv_lanczos_kernels.hpp"
 
@@ -104,15 +104,6 @@ int fused_step_enqueue(hxv_handle* h, bool real, const double2* q, const double2
 
 struct LzBuf {
   double2 *q, *qm, *w;
-};
-// a small device array of one driver call (hipMalloc'ed into p by the driver): freed on every way out, after the stream has drained
-struct DevFree {
-  hipStream_t st;
-  double* p = nullptr;
-  ~DevFree() {
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(p);
-  }
 };
 
 // Lanczos recurrence on device.  Two implementations of one step:
@@ -239,9 +230,10 @@ struct LzRunner {
   // hxv_time_lanczos's pair): ev[0] is recorded after the hand-over and before the first captured iteration, ev[1]
   // after the last one, and waited for.
   int run_device_only(double beta, int nmax, double* ab, hipEvent_t* ev, const char* who) {
-    DevFree d_ab{h->stream};
-    HIPCHK(hipMalloc((void**)&d_ab.p, (size_t)2 * nmax * sizeof(double)));
-    HIPCHK(hipMemsetAsync(d_ab.p, 0, (size_t)2 * nmax * sizeof(double), h->stream));
+    CallScope scratch(h);
+    double* d_ab = nullptr;
+    HIPCHK(scratch.take_device((size_t)2 * nmax * sizeof(double), &d_ab));
+    HIPCHK(hipMemsetAsync(d_ab, 0, (size_t)2 * nmax * sizeof(double), h->stream));
     const double s1 = 1.0 / beta, bprev = 1.0 / sc.s_cur;
     const double init[2] = {s1, 1.0 / (s1 * bprev)};   // s_1 = 1/beta_1 ; c_1 = beta_1/beta_0, rounded like LzScale::next() + c()
     const double one = 1.0;
@@ -250,7 +242,7 @@ struct LzRunner {
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (init and one are read by asynchronous copies)
     if (e == hipSuccess && ev) e = hipEventRecord(ev[0], h->stream);
     if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    int rc = run_device_iterations(nmax, d_ab.p, d_ab.p + nmax);
+    int rc = run_device_iterations(nmax, d_ab, d_ab + nmax);
     if (rc) return rc;
     if (ev) {
       e = hipEventRecord(ev[1], h->stream);
@@ -258,7 +250,7 @@ struct LzRunner {
       if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
     }
     if (ab) {
-      e = hipMemcpyAsync(ab, d_ab.p, (size_t)2 * nmax * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+      e = hipMemcpyAsync(ab, d_ab, (size_t)2 * nmax * sizeof(double), hipMemcpyDeviceToHost, h->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
       if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string("reading alpha/beta back: ") + hipGetErrorString(e));
     }
@@ -321,29 +313,14 @@ int ensure_lz(hxv_handle* h, bool real) {
   return HXV_OK;
 }
 
-// What a driver call took from the device-buffer cache goes back to it when the call returns, after the stream has drained.
-struct PoolGuard {
-  hxv_handle* h;
-  std::vector<void*> p;
-  int take(size_t bytes, void** out) {
-    HIPCHK(pool_alloc(h->device, bytes, out));
-    p.push_back(*out);
-    return HXV_OK;
-  }
-  ~PoolGuard() {
-    if (!p.empty()) (void)hipStreamSynchronize(h->stream);
-    for (void* q : p) pool_free(h->device, q);
-  }
-};
-
 // A start vector that lives in one of the handle's gather buffers (built at hxv_slab_home) would be zeroed by ensure_lz, which clears the
 // slab's place in all three before the driver reads its input: such a vector is copied to a staging slab first (one slab copy per RUN).
-// The staging buffer goes into `pooled`, which returns it after the run.
-int stage_start_vector(hxv_handle* h, const void*& d_vin, PoolGuard& pooled) {
+// The staging buffer belongs to the call's scope, which returns it after the run.
+int stage_start_vector(hxv_handle* h, const void*& d_vin, CallScope& pooled) {
   if (!comm_ready(h) || !comm_in_gather(h, d_vin)) return HXV_OK;
   const size_t bytes = (size_t)h->host.pitch * std::max(h->host.qdw, 1) * sizeof(double2);
   void* tmp = nullptr;
-  if (int rc = pooled.take(bytes, &tmp)) return rc;
+  HIPCHK(pooled.take(bytes, &tmp));
   HIPCHK(hipMemcpyAsync(tmp, d_vin, bytes, hipMemcpyDeviceToDevice, h->stream));
   d_vin = tmp;
   return HXV_OK;
@@ -426,14 +403,14 @@ int tridiag_run(hxv_handle* h, const char* who, int rc_args, const void* d_vin, 
   // scratch of a run WITH probes, from the device-buffer cache and sized by nprobes: block partials of the real-vector check (start vector and
   // probes, side by side), block partials and sums of a step's overlaps.  Without probes the check's partials are the handle's own.
   double* d_ws = nullptr;
-  PoolGuard pooled{h, {}};  // (with the staged start vector and the real-mode copies of the probes)
+  CallScope pooled(h);  // (with the staged start vector and the real-mode copies of the probes)
   size_t n_chk = 0, n_part = 0;
   // what a rank decides from its own arguments and resources, agreed on before the first collective
   auto resources = [&]() -> int {
     if (rc_args || nprobes == 0) return rc_args;
     n_chk = (size_t)(1 + nprobes) * RED_BLOCKS;
     n_part = (size_t)2 * nprobes * RED_BLOCKS;
-    if (int rc = pooled.take((n_chk + n_part + 2 * nprobes) * sizeof(double), (void**)&d_ws)) return rc;
+    HIPCHK(pooled.take((n_chk + n_part + 2 * nprobes) * sizeof(double), &d_ws));
     // page-locked staging for the overlaps of every step: a copy into the caller's pageable array could make the runtime wait per step
     const int64_t want = (int64_t)2 * nprobes * nlanc;
     if (want > h->probe_ov_n) {
@@ -473,7 +450,7 @@ int tridiag_run(hxv_handle* h, const char* who, int rc_args, const void* d_vin, 
     if (rc_pre) return rc_pre;
     int r = stage_start_vector(h, d_vin, pooled);  // (a start vector at hxv_slab_home: staged before its home is cleared)
     if (!r) r = ensure_lz(h, real);
-    for (int j = 0; real && j < nprobes && !r; ++j) r = pooled.take(real_bytes, (void**)&real_probe[j]);
+    for (int j = 0; real && j < nprobes && !r; ++j) HIPCHK(pooled.take(real_bytes, &real_probe[j]));
     return r;
   };
   int rc = comm_agree(h, prepare());  // (a rank that could not allocate tells its peers before the first all-reduce)
@@ -729,12 +706,12 @@ int tridiag_pair_run(hxv_handle* h, const char* who, int rc_args, const void* d_
   if (int rcc = need_comm(h, "device Lanczos")) return rcc;
   if (!h->lz_fused) return fail(HXV_ERR_UNSUPPORTED, std::string(who) + " needs the fused recurrence (option lanczos_fused)");
   HIPCHK(hipSetDevice(h->device));
-  PoolGuard pooled{h, {}};  // (staged start vectors; with probes their real copies and the scratch of the check and the overlaps)
+  CallScope pooled(h);  // (the scalar blocks; staged start vectors; with probes their real copies and the scratch of the check and the overlaps)
   const int64_t n = lz_len(h, false);
   const int g = grid_for(n);
   // scalars: the LzSlot block of component a, the one of b LZ_PAIR behind it (the handle's d_scalars has room for one only); the block
   // partials of the start vectors' check behind them
-  DevFree sc_mem{h->stream};
+  double* d_sc_mem = nullptr;
   // scratch of a run WITH probes, from the device-buffer cache and sized by nprobes: block partials of Im^2 (start vectors, then one row of
   // RED_BLOCKS per probe, g of each used, side by side for the one reduction), block partials and sums of a step's overlaps
   double* d_ws = nullptr;
@@ -749,11 +726,10 @@ int tridiag_pair_run(hxv_handle* h, const char* who, int rc_args, const void* d_
     if (!r) r = ensure_wt(h);
     if (!r) r = ensure_lz_partial(h, 2 * lz_pass_a_workgroups(h, false));
     if (r) return r;
-    HIPCHK(hipMalloc((void**)&sc_mem.p, (size_t)(2 * LZ_PAIR + 3 * RED_BLOCKS) * sizeof(double)));
+    HIPCHK(pooled.take_device((size_t)(2 * LZ_PAIR + 3 * RED_BLOCKS) * sizeof(double), &d_sc_mem));
     if (nprobes == 0) return HXV_OK;
-    if ((r = pooled.take((n_chk + n_part + 2 * nprobes) * sizeof(double), (void**)&d_ws))) return r;
-    for (int j = 0; j < nprobes; ++j)
-      if ((r = pooled.take((size_t)std::max<int64_t>(n, 1) * sizeof(double), (void**)&pr.p[j]))) return r;
+    HIPCHK(pooled.take((n_chk + n_part + 2 * nprobes) * sizeof(double), &d_ws));
+    for (int j = 0; j < nprobes; ++j) HIPCHK(pooled.take((size_t)std::max<int64_t>(n, 1) * sizeof(double), &pr.p[j]));
     // page-locked staging for the overlaps of every step (a slot of 2*nprobes sums per step), shared with tridiag_run
     const int64_t want = (int64_t)2 * nprobes * nlanc;
     if (want > h->probe_ov_n) {
@@ -767,7 +743,7 @@ int tridiag_pair_run(hxv_handle* h, const char* who, int rc_args, const void* d_
   };
   int rc = comm_agree(h, prepare());
   if (rc) return rc;
-  double* const d_sc = sc_mem.p;
+  double* const d_sc = d_sc_mem;
   double* d_p0 = nprobes ? d_ws : d_sc + 2 * LZ_PAIR;  // (Im^2 of the start vectors; the probes' rows follow it at a distance of g)
   double* d_p1 = d_sc + 2 * LZ_PAIR + RED_BLOCKS;
   double* d_p2 = d_p1 + RED_BLOCKS;

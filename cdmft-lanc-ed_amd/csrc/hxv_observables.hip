@@ -23,12 +23,12 @@
 #include <algorithm>
 #include <cstring>
 
-#include "hxv_handle.hpp"
+#include "hxv_call_scope.hpp"
 
 using namespace hxv;
 
-namespace hxv {
-struct SectorImage::ObsTables {
+namespace {
+struct ObsTables : DeviceTables {
   int nimp = 0, nw = 0, np = 0, gtot = 0;
   int64_t nent = 0, ndwp = 0;
   // up side (rows of one column): groups [seg_ptr[g], seg_ptr[g+1]) of (row_a, row_b, sign), g < nw: W bins (row_a == row_b), then np pair groups
@@ -37,22 +37,7 @@ struct SectorImage::ObsTables {
   // dw side (local columns): pairs [dwp_ptr[c], dwp_ptr[c+1]) of (partner column slot, pair index, sign); columns by dw impurity bits
   int32_t *dwp_ptr = nullptr, *dwp_slot = nullptr, *dwp_p = nullptr, *dwbin_ptr = nullptr, *dwbin_cols = nullptr;
   int8_t* dwp_s = nullptr;
-  void* base = nullptr;
-  int device = -1;
-  int64_t bytes = 0;
-  ~ObsTables() {
-    if (!base) return;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(device);
-    (void)hipFree(base);
-    if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
-  }
 };
-}  // namespace hxv
-
-namespace {
-using ObsTables = SectorImage::ObsTables;
 constexpr int OBS_THREADS = 256;
 constexpr int OBS_WAVES = OBS_THREADS / 64;
 constexpr int OBS_MAX_NIMP = 10;  // record of 4^10 + 400 doubles (8 MB); the reference's own cluster_density_matrix is 4^Nimp squared
@@ -316,46 +301,28 @@ int hxv_observables_accumulate(hxv_handle* h, const void* d_psi, double weight, 
   // rank-local preparation: tables (once per sector image), scratch; every rank learns whether all could go on
   int rc_local = HXV_OK;
   std::shared_ptr<ObsTables> t;
-  {
-    std::lock_guard<std::mutex> lk(h->img->obs_mu);
-    if (!h->img->obs) {
-      auto nt = std::make_shared<ObsTables>();
-      const std::string err = build_tables(s, nimp, h->device, *nt);
-      if (err.empty())
-        h->img->obs = nt;
-      else
-        rc_local = fail(err.rfind("observables tables", 0) == 0 ? HXV_ERR_HIP : HXV_ERR_STATE, err);
-    }
-    t = h->img->obs;
-  }
+  rc_local = h->img->tables.get("observables", "", 1, t, [&](std::shared_ptr<ObsTables>& nt) {
+    nt = std::make_shared<ObsTables>();
+    const std::string err = build_tables(s, nimp, h->device, *nt);
+    return err.empty() ? HXV_OK : fail(err.rfind("observables tables", 0) == 0 ? HXV_ERR_HIP : HXV_ERR_STATE, err);
+  });
   const int np = nimp * nimp, gtot = (1 << nimp) + 2 * np;
   const int64_t nww = (int64_t)1 << (2 * nimp), nrec = nww + 4 * (int64_t)np;
   double2 *d_col = nullptr, *d_full = nullptr;
   double* d_rec = nullptr;
+  CallScope scratch(h);
   if (rc_local == HXV_OK) {
-    hipError_t e1 = pool_alloc(h->device, std::max<size_t>((size_t)s.qdw * gtot, 1) * sizeof(double2), (void**)&d_col);
-    hipError_t e2 = pool_alloc(h->device, (size_t)nrec * sizeof(double), (void**)&d_rec);
-    hipError_t e3 = split ? pool_alloc(h->device, std::max<size_t>((size_t)s.nranks * s.cmax * s.pitch, 1) * sizeof(double2), (void**)&d_full) : hipSuccess;
+    hipError_t e1 = scratch.take(std::max<size_t>((size_t)s.qdw * gtot, 1) * sizeof(double2), &d_col);
+    hipError_t e2 = scratch.take((size_t)nrec * sizeof(double), &d_rec);
+    hipError_t e3 = split ? scratch.take(std::max<size_t>((size_t)s.nranks * s.cmax * s.pitch, 1) * sizeof(double2), &d_full) : hipSuccess;
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) rc_local = fail(HXV_ERR_HIP, "hxv_observables_accumulate: scratch buffers");
   }
-  auto release = [&]() {
-    (void)hipStreamSynchronize(st);
-    if (d_col) pool_free(h->device, d_col);
-    if (d_rec) pool_free(h->device, d_rec);
-    if (d_full) pool_free(h->device, d_full);
-  };
   int rc = split ? comm_agree(h, rc_local) : rc_local;
-  if (rc) {
-    release();
-    return rc;
-  }
+  if (rc) return rc;
   const double2* psi = (const double2*)d_psi;
   if (split) {
     rc = comm_allgather_slab(h, psi, d_full, st);
-    if (rc) {
-      release();
-      return rc;
-    }
+    if (rc) return rc;
   }
   if (s.qdw > 0) {
     const dim3 grid((unsigned)s.qdw), block(OBS_THREADS);
@@ -367,20 +334,14 @@ int hxv_observables_accumulate(hxv_handle* h, const void* d_psi, double weight, 
   hipLaunchKernelGGL(obs_reduce_kernel, dim3((unsigned)(nww + 2 * np)), dim3(OBS_THREADS), 0, st, (const double2*)d_col, s.qdw, nimp, t->nw,
                      t->np, t->dwbin_ptr, t->dwbin_cols, d_rec);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    release();
-    return fail(HXV_ERR_HIP, std::string("observables kernels: ") + hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string("observables kernels: ") + hipGetErrorString(e));
   if (split) {
     rc = comm_allreduce_sum(h, d_rec, (size_t)nrec, st);
-    if (rc) {
-      release();
-      return rc;
-    }
+    if (rc) return rc;
   }
   std::vector<double> raw((size_t)nrec);
   e = hipMemcpyAsync(raw.data(), d_rec, (size_t)nrec * sizeof(double), hipMemcpyDeviceToHost, st);
-  release();
+  scratch.release();  // (synchronises the stream: raw is read below)
   if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string("hxv_observables_accumulate: ") + hipGetErrorString(e));
   // R_s(js,is) = conj R_s(is,js): c^+_js c_is is the adjoint of c^+_is c_js, and the device computes is < js only
   for (int spin = 0; spin < 2; ++spin) {

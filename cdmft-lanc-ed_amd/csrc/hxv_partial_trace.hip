@@ -15,39 +15,24 @@
 // library includes as well (tests/device/partial_trace_kernels_check.hip); the tables' owner and the two entry points are here.
 #include <hip/hip_runtime.h>
 
-#include "hxv_handle.hpp"
+#include "hxv_call_scope.hpp"
 #include "hxv_partial_trace_host.hpp"
 #include "hxv_partial_trace_kernels.hpp"
 
 namespace hxv {
-struct PtTables : PtHostTables {
+struct PtTables : PtHostTables, DeviceTables {
   std::string name;  // "cluster density matrix": the head of the error text
   PtClass* d_cls = nullptr;
   PtItem* d_items = nullptr;
   uint32_t *d_rows = nullptr, *d_cols = nullptr, *d_tiles = nullptr;
   int32_t *d_el_cnt = nullptr, *d_el_stride = nullptr;
   int64_t* d_el_src = nullptr;
-  void* base = nullptr;
-  int device = -1;
-  int64_t bytes = 0;
-  ~PtTables() {
-    if (!base) return;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(device);
-    (void)hipFree(base);
-    if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
-  }
 };
-}  // namespace hxv
 
-namespace hxv {
 int pt_make_tables(const hxv_handle* h, int nsub, const PtGroups& up, const PtGroups& dw, int small_n, const char* name, std::shared_ptr<PtTables>& out) {
   const SectorHost& s = h->host;
-  int ncu = 0;
-  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || ncu < 1) ncu = 256;
   auto t = std::make_shared<PtTables>();
-  const std::string err = pt_build(PtSector{nsub, s.nup, s.ndw, s.dimup, s.dimdw, s.nranks, s.cmax, s.qdw, s.dw0}, up, dw, small_n, ncu, name, *t);
+  const std::string err = pt_build(PtSector{nsub, s.nup, s.ndw, s.dimup, s.dimdw, s.nranks, s.cmax, s.qdw, s.dw0}, up, dw, small_n, compute_units(h->device), name, *t);
   if (!err.empty()) return fail(HXV_ERR_STATE, err);
   t->name = name;
   t->device = h->device;
@@ -66,6 +51,11 @@ int pt_make_tables(const hxv_handle* h, int nsub, const PtGroups& up, const PtGr
   return HXV_OK;
 }
 
+int pt_stored_tables(hxv_handle* h, const char* family, const std::string& key, size_t cap, std::shared_ptr<PtTables>& out,
+                     const std::function<int(std::shared_ptr<PtTables>&)>& build) {
+  return h->img->tables.get(family, key, cap, out, build);
+}
+
 int pt_accumulate(hxv_handle* h, const std::shared_ptr<PtTables>& t, int rc_local, const void* d_psi, double weight, bool accumulate, double* out,
                   const char* what) {
   const SectorHost& s = h->host;
@@ -73,30 +63,19 @@ int pt_accumulate(hxv_handle* h, const std::shared_ptr<PtTables>& t, int rc_loca
   hipStream_t st = h->stream;
   // rank-local preparation: scratch; every rank learns whether all could go on
   double2 *d_part = nullptr, *d_out = nullptr, *d_full = nullptr;
+  CallScope scratch(h);
   if (rc_local == HXV_OK) {
-    hipError_t e1 = pool_alloc(h->device, std::max<size_t>((size_t)t->partial_elems, 1) * sizeof(double2), (void**)&d_part);
-    hipError_t e2 = pool_alloc(h->device, std::max<size_t>((size_t)t->out_elems, 1) * sizeof(double2), (void**)&d_out);
-    hipError_t e3 = split ? pool_alloc(h->device, std::max<size_t>((size_t)s.nranks * s.cmax * s.pitch, 1) * sizeof(double2), (void**)&d_full) : hipSuccess;
+    hipError_t e1 = scratch.take(std::max<size_t>((size_t)t->partial_elems, 1) * sizeof(double2), &d_part);
+    hipError_t e2 = scratch.take(std::max<size_t>((size_t)t->out_elems, 1) * sizeof(double2), &d_out);
+    hipError_t e3 = split ? scratch.take(std::max<size_t>((size_t)s.nranks * s.cmax * s.pitch, 1) * sizeof(double2), &d_full) : hipSuccess;
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) rc_local = fail(HXV_ERR_HIP, std::string(what) + ": scratch buffers");
   }
-  auto release = [&]() {
-    (void)hipStreamSynchronize(st);
-    if (d_part) pool_free(h->device, d_part);
-    if (d_out) pool_free(h->device, d_out);
-    if (d_full) pool_free(h->device, d_full);
-  };
   int rc = split ? comm_agree(h, rc_local) : rc_local;
-  if (rc) {
-    release();
-    return rc;
-  }
+  if (rc) return rc;
   const double2* psi = (const double2*)d_psi;
   if (split) {
     rc = comm_allgather_slab(h, psi, d_full, st);
-    if (rc) {
-      release();
-      return rc;
-    }
+    if (rc) return rc;
   }
   const double2* src = split ? (const double2*)d_full : psi;
   const int* ni = t->nitems;
@@ -112,20 +91,14 @@ int pt_accumulate(hxv_handle* h, const std::shared_ptr<PtTables>& t, int rc_loca
   hipLaunchKernelGGL(pt_reduce_kernel, dim3((unsigned)((t->out_elems + PT_THREADS - 1) / PT_THREADS)), dim3(PT_THREADS), 0, st,
                      (const double2*)d_part, t->d_el_src, t->d_el_cnt, t->d_el_stride, t->out_elems, d_out);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    release();
-    return fail(HXV_ERR_HIP, t->name + " kernels: " + hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(HXV_ERR_HIP, t->name + " kernels: " + hipGetErrorString(e));
   if (split) {
     rc = comm_allreduce_sum(h, (double*)d_out, (size_t)(2 * t->out_elems), st);
-    if (rc) {
-      release();
-      return rc;
-    }
+    if (rc) return rc;
   }
   std::vector<double2> raw((size_t)t->out_elems);
   e = hipMemcpyAsync(raw.data(), d_out, (size_t)t->out_elems * sizeof(double2), hipMemcpyDeviceToHost, st);
-  release();
+  scratch.release();  // (synchronises the stream: raw is read below)
   if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
   scatter(*t, raw, weight, accumulate, out);
   return HXV_OK;

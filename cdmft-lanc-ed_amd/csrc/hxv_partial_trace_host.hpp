@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -206,6 +207,10 @@ struct PtTables;
 // builds the tables of the handle's sector from its groups and uploads them; name: the matrix's ("cluster density matrix"), the head of the
 // error text.  HXV_OK, or the failure as recorded
 int pt_make_tables(const hxv_handle* h, int nsub, const PtGroups& up, const PtGroups& dw, int small_n, const char* name, std::shared_ptr<PtTables>& out);
+// out = the tables of (family, key) kept with the handle's sector image (TableStore, hxv_handle.hpp), the family's `cap` most recently used;
+// `build` makes them when they are not there.  HXV_OK, or what build returned: then nothing is stored and out stays null
+int pt_stored_tables(hxv_handle* h, const char* family, const std::string& key, size_t cap, std::shared_ptr<PtTables>& out,
+                     const std::function<int(std::shared_ptr<PtTables>&)>& build);
 // out (+)= weight * rho of the device vector d_psi.  t: the tables, null where this rank could not make them and rc_local says why: every
 // rank of a split sector learns of it and returns.  what: the entry point's name, for the error text
 int pt_accumulate(hxv_handle* h, const std::shared_ptr<PtTables>& t, int rc_local, const void* d_psi, double weight, bool accumulate, double* out,

@@ -95,6 +95,11 @@ void pool_free(int device, void* ptr) {
     (void)hipFree(ptr);
   }
 }
+
+int64_t pool_live_blocks(int device) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return (int64_t)g_pools[device].live.size();
+}
 }  // namespace hxv
 
 extern "C" {

@@ -42,30 +42,16 @@ int hxv_reduced_dm_accumulate(hxv_handle* h, const void* d_psi, uint32_t orbital
   if (__builtin_popcount(orbital_mask) > RDM_MAX_NRED) return fail(HXV_ERR_UNSUPPORTED, "hxv_reduced_dm_accumulate: more than 4 orbitals in the mask");
   if (s.nranks > 1 && !comm_ready(h)) return fail(HXV_ERR_STATE, "hxv_reduced_dm_accumulate on a split sector needs the communicator (hxv_comm_init after opening it)");
   HIPCHK(hipSetDevice(h->device));
-  int rc_local = HXV_OK;
+  // HXV_RDM_PAIR_KERNEL=0 sends every class to the tile kernel (the A/B hook of scripts/reduced_dm_bench.py)
+  const char* ab = std::getenv("HXV_RDM_PAIR_KERNEL");
+  const int small_n = (ab && ab[0] == '0' && !ab[1]) ? 0 : PT_PAIR_N;
+  const uint64_t key = (uint64_t)orbital_mask | ((uint64_t)fermi_sign << 32) | ((uint64_t)(small_n == 0) << 33);
   std::shared_ptr<PtTables> t;
-  {
-    // HXV_RDM_PAIR_KERNEL=0 sends every class to the tile kernel (the A/B hook of scripts/reduced_dm_bench.py)
-    const char* ab = std::getenv("HXV_RDM_PAIR_KERNEL");
-    const int small_n = (ab && ab[0] == '0' && !ab[1]) ? 0 : PT_PAIR_N;
-    const uint64_t key = (uint64_t)orbital_mask | ((uint64_t)fermi_sign << 32) | ((uint64_t)(small_n == 0) << 33);
-    std::lock_guard<std::mutex> lk(h->img->rdm_mu);
-    auto& cache = h->img->rdm;
-    for (size_t i = 0; i < cache.size() && !t; ++i)
-      if (cache[i].first == key) {
-        t = cache[i].second;
-        std::rotate(cache.begin() + i, cache.begin() + i + 1, cache.end());  // most recently used last
-      }
-    if (!t) {
-      PtGroups up, dw;
-      const std::string err = reduced_dm_groups(s, orbital_mask, fermi_sign, up, dw);
-      rc_local = err.empty() ? pt_make_tables(h, __builtin_popcount(orbital_mask), up, dw, small_n, "reduced density matrix", t) : fail(HXV_ERR_STATE, err);
-      if (t) {
-        if (cache.size() >= RDM_CACHE) cache.erase(cache.begin());  // a call under way keeps its tables alive through its own reference
-        cache.emplace_back(key, t);
-      }
-    }
-  }
+  const int rc_local = pt_stored_tables(h, "reduced density matrix", std::string((const char*)&key, sizeof key), RDM_CACHE, t, [&](std::shared_ptr<PtTables>& nt) {
+    PtGroups up, dw;
+    const std::string err = reduced_dm_groups(s, orbital_mask, fermi_sign, up, dw);
+    return err.empty() ? pt_make_tables(h, __builtin_popcount(orbital_mask), up, dw, small_n, "reduced density matrix", nt) : fail(HXV_ERR_STATE, err);
+  });
   return pt_accumulate(h, t, rc_local, d_psi, weight, accumulate != 0, rdm, "hxv_reduced_dm_accumulate");
 }
 

@@ -7,75 +7,56 @@
 #include <string>
 #include <vector>
 
-#include "hxv_handle.hpp"
+#include "hxv_handle.hpp"  // (no per-call scratch here: the tables live with `to`'s image, the sums in the handle's own scalars)
 #include "hxv_spin_pair_host.hpp"
 #include "hxv_spin_pair_kernels.hpp"
-
-namespace hxv {
-// The tables of one (source sector and its row order, create_up, create_dw) into the image's sector: a block of Ns up tables and Ns dw tables,
-// one per orbital, filled when an orbital is first asked for.
-struct SpTables {
-  std::string key;
-  int device = -1;
-  int32_t* d_up = nullptr;  // [ns][dimup_to]
-  int32_t* d_dw = nullptr;  // [ns][dimdw_to]
-  uint32_t have_up = 0, have_dw = 0;
-  ~SpTables() {
-    if (!d_up && !d_dw) return;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(device);
-    if (d_up) (void)hipFree(d_up);
-    if (d_dw) (void)hipFree(d_dw);
-    if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
-  }
-};
-}  // namespace hxv
 
 using namespace hxv;
 
 namespace {
 constexpr size_t SP_CACHE = 8;  // source sectors x flags kept per target image: the four neighbours of one solve, both directions
 
+// The tables of one (source sector and its row order, create_up, create_dw) into the image's sector: a block of Ns up tables and Ns dw tables,
+// one per orbital, filled when an orbital is first asked for.
+struct SpTables : DeviceTables {
+  int32_t* d_up = nullptr;  // [ns][dimup_to]
+  int32_t* d_dw = nullptr;  // [ns][dimdw_to]
+  uint32_t have_up = 0, have_dw = 0;
+};
+
 bool has_maps(const hxv_handle* h) { return !h->host.map_up.empty() && !h->host.map_dw.empty() && h->host.panel_rows == 0; }
 
-// the cached tables of (from -> to, flags) with every orbital of the plan filled in; called under to->img->sp_mu
-int tables_for(hxv_handle* from, hxv_handle* to, int create_up, int create_dw, const SpPlan& plan, std::shared_ptr<SpTables>& out) {
+// the two empty blocks of a new table set on `to`'s device
+int make_tables(const hxv_handle* to, std::shared_ptr<SpTables>& t) {
+  const SectorHost& b = to->host;
+  t = std::make_shared<SpTables>();
+  t->device = to->device;
+  hipError_t e = hipMalloc((void**)&t->d_up, (size_t)b.ns * b.dimup * sizeof(int32_t));
+  if (e == hipSuccess) t->more.push_back(t->d_up);
+  if (e == hipSuccess) e = hipMalloc((void**)&t->d_dw, (size_t)b.ns * b.dimdw * sizeof(int32_t));
+  if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string("hxv_apply_spin_pair tables: ") + hipGetErrorString(e));
+  t->more.push_back(t->d_dw);
+  return HXV_OK;
+}
+
+// every orbital of the plan that the set does not hold yet: built and uploaded (under the store's lock)
+int fill_tables(const hxv_handle* from, const hxv_handle* to, int create_up, int create_dw, const SpPlan& plan, SpTables& t) {
   const SectorHost &a = from->host, &b = to->host;
-  auto& cache = to->img->sp;
-  const std::string key = spin_pair_key(a, create_up, create_dw);
-  std::shared_ptr<SpTables> t;
-  for (size_t i = 0; i < cache.size() && !t; ++i)
-    if (cache[i]->key == key) {
-      t = cache[i];
-      std::rotate(cache.begin() + i, cache.begin() + i + 1, cache.end());  // most recently used last
-    }
-  if (!t) {
-    t = std::make_shared<SpTables>();
-    t->key = key;
-    t->device = to->device;
-    hipError_t e = hipMalloc((void**)&t->d_up, (size_t)b.ns * b.dimup * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&t->d_dw, (size_t)b.ns * b.dimdw * sizeof(int32_t));
-    if (e != hipSuccess) return fail(HXV_ERR_HIP, std::string("hxv_apply_spin_pair tables: ") + hipGetErrorString(e));
-    if (cache.size() >= SP_CACHE) cache.erase(cache.begin());  // a call under way keeps its tables alive through its own reference
-    cache.push_back(t);
-  }
   std::vector<int32_t> tab;
   for (int u = 0; u < plan.nuq; ++u) {
     const int o = plan.uq_orb[u];
-    if (t->have_up >> o & 1u) continue;
+    if (t.have_up >> o & 1u) continue;
     spin_pair_up_table(a, b, o, create_up, tab);
-    HIPCHK(hipMemcpy(t->d_up + (size_t)o * b.dimup, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    t->have_up |= 1u << o;
+    HIPCHK(hipMemcpy(t.d_up + (size_t)o * b.dimup, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    t.have_up |= 1u << o;
   }
   for (int d = 0; d < plan.ndq; ++d) {
     const int o = plan.dq_orb[d];
-    if (t->have_dw >> o & 1u) continue;
+    if (t.have_dw >> o & 1u) continue;
     spin_pair_dw_table(a, b, o, create_dw, tab);
-    HIPCHK(hipMemcpy(t->d_dw + (size_t)o * b.dimdw, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    t->have_dw |= 1u << o;
+    HIPCHK(hipMemcpy(t.d_dw + (size_t)o * b.dimdw, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    t.have_dw |= 1u << o;
   }
-  out = t;
   return HXV_OK;
 }
 }  // namespace
@@ -99,11 +80,11 @@ int hxv_apply_spin_pair(hxv_handle* from, hxv_handle* to, int32_t create_up, int
   if (!perr.empty()) return fail(HXV_ERR_ARG, "hxv_apply_spin_pair: " + perr);
   HIPCHK(hipSetDevice(to->device));
   std::shared_ptr<SpTables> t;
-  {
-    std::lock_guard<std::mutex> lk(to->img->sp_mu);
-    const int rc = tables_for(from, to, create_up ? 1 : 0, create_dw ? 1 : 0, plan, t);
-    if (rc) return rc;
-  }
+  const int cu = create_up ? 1 : 0, cd = create_dw ? 1 : 0;
+  const int rc = to->img->tables.get(
+      "spin pair", spin_pair_key(a, cu, cd), SP_CACHE, t, [&](std::shared_ptr<SpTables>& nt) { return make_tables(to, nt); },
+      [&](SpTables& have) { return fill_tables(from, to, cu, cd, plan, have); });
+  if (rc) return rc;
   SpTerms tm{};
   tm.nterms = plan.nterms;
   tm.nuq = plan.nuq;

@@ -32,7 +32,7 @@
 // All element offsets are int64 (a C5 slab is more than 2^31 bytes); both grids loop over their y extent instead of exceeding 65535.
 #include <hip/hip_runtime.h>
 
-#include "hxv_handle.hpp"
+#include "hxv_call_scope.hpp"
 #include "hxv_twin_kernels.hpp"
 
 using namespace hxv;
@@ -69,9 +69,10 @@ int twin_vector_split(hxv_handle* from, hxv_handle* to, const void* d_psi, void*
   double2 *d_send = nullptr, *d_recv = nullptr;
   int64_t* d_tab = nullptr;
   int rc_local = HXV_OK;
-  hipError_t e1 = pool_alloc(to->device, (size_t)send_ptr[P] * sizeof(double2), (void**)&d_send);
-  hipError_t e2 = pool_alloc(to->device, (size_t)recv_ptr[P] * sizeof(double2), (void**)&d_recv);
-  hipError_t e3 = hipMalloc((void**)&d_tab, tab.size() * sizeof(int64_t));
+  CallScope scratch(to);
+  hipError_t e1 = scratch.take((size_t)send_ptr[P] * sizeof(double2), &d_send);
+  hipError_t e2 = scratch.take((size_t)recv_ptr[P] * sizeof(double2), &d_recv);
+  hipError_t e3 = scratch.take_device(tab.size() * sizeof(int64_t), &d_tab);
   if (e3 == hipSuccess) e3 = hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, st);
   for (auto& ev : to->tw_ev)
     if (!ev && e3 == hipSuccess) e3 = hipEventCreate(&ev);
@@ -79,19 +80,9 @@ int twin_vector_split(hxv_handle* from, hxv_handle* to, const void* d_psi, void*
     (void)hipGetLastError();
     rc_local = fail(HXV_ERR_HIP, "hxv_twin_vector: staging buffers and table of the split map");
   }
-  auto release = [&]() {
-    (void)hipStreamSynchronize(st);
-    if (e1 == hipSuccess && d_send) pool_free(to->device, d_send);
-    if (e2 == hipSuccess && d_recv) pool_free(to->device, d_recv);
-    if (d_tab) (void)hipFree(d_tab);
-  };
   int rcx = comm_agree(to, rc_local);
-  if (rcx) {
-    release();
-    return rcx;
-  }
+  if (rcx) return rcx;
   auto step_failed = [&](const char* what, hipError_t e) {
-    release();
     return fail(HXV_ERR_HIP, std::string("hxv_twin_vector: ") + what + ": " + hipGetErrorString(e));
   };
   hipError_t e = hipEventRecord(to->tw_ev[0], st);
@@ -105,10 +96,7 @@ int twin_vector_split(hxv_handle* from, hxv_handle* to, const void* d_psi, void*
   }
   (void)hipEventRecord(to->tw_ev[1], st);
   rcx = comm_sendrecv_cols(to, d_send, send_ptr.data(), d_recv, recv_ptr.data(), sizeof(double2), st);
-  if (rcx) {
-    release();
-    return rcx;
-  }
+  if (rcx) return rcx;
   (void)hipEventRecord(to->tw_ev[2], st);
   {
     const unsigned gx = (unsigned)((b.pitch + TW_THREADS - 1) / TW_THREADS), gy = (unsigned)std::min(b.qdw, 65535);
@@ -124,7 +112,6 @@ int twin_vector_split(hxv_handle* from, hxv_handle* to, const void* d_psi, void*
     float ms = 0.f;
     to->twin_last_us[i] = hipEventElapsedTime(&ms, to->tw_ev[i], to->tw_ev[i + 1]) == hipSuccess ? (int64_t)(ms * 1e3f + 0.5f) : -1;
   }
-  release();
   return HXV_OK;
 }
 }  // namespace

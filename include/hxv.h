@@ -729,7 +729,9 @@ int hxv_get_diag(const hxv_handle *h, double *diag);
  * driver read-backs ("pass_b_order_last": the phase order the last pass-B launch ran, 1 = out-of-block sums in registers, 0 = the earlier
  * order [eight pairs per thread, row-major scratch patches, a largest block that leaves no room for wt_cols - 1 dead columns, debug bit 8192],
  * -1 = no launch since the plan was made; "lanczos_real_last", "eigh_last_full_passes", "eigh_last_local_passes", "eigh_last_search_products",
- * "eigh_last_check_products", "slab_copies", "allreduce_count" (the sum all-reduces a split sector's drivers have made on this handle); which restart code the last hxv_eigh_lowest ran: "eigh_last_restarts" thick restarts of the search
+ * "eigh_last_check_products", "slab_copies", "allreduce_count" (the sum all-reduces a split sector's drivers have made on this handle), "pool_live_blocks" (the blocks of the
+ * device-buffer cache that are handed out on the handle's DEVICE and not yet returned -- every handle's vectors and work buffers and whatever a
+ * driver call under way holds; a driver call leaves it where it found it, however it returns); which restart code the last hxv_eigh_lowest ran: "eigh_last_restarts" thick restarts of the search
  * round, "eigh_last_fused_restarts" those whose rotation also measured the residual vector, "eigh_last_fused_first_steps" restart cycles whose
  * first step removed the arrow and measured in one pass) and what the open cost ("open_cache_hit", "open_us_host|plan|upload|total").
  * Every option of groups 1 and 2 reads back the value hxv_set_option stored ("tile_bits_up|_dw": the block bits of the plan in use;
