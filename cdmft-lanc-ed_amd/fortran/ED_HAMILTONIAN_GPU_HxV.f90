@@ -46,6 +46,7 @@ module ED_HAMILTONIAN_GPU_HXV
   public :: gpu_sp_lanc_tridiag_pair_probes_dev
   public :: gpu_apply_density_ops_dev
   public :: gpu_apply_spin_pair_dev
+  public :: gpu_apply_one_body_dev
   public :: gpu_vector_to_host
   public :: gpu_vector_from_host
   public :: gpu_free_vector
@@ -408,6 +409,14 @@ module ED_HAMILTONIAN_GPU_HXV
        real(c_double),intent(in)     :: coef(*)
        real(c_double)                :: norm2
      end function hxv_apply_spin_pair
+     integer(c_int) function hxv_apply_one_body(h,nterms,spin,orb_to,orb_from,coef,subtract_mean,d_psi,d_out,mean,norm2) bind(C,name="hxv_apply_one_body")
+       import :: c_int, c_int32_t, c_ptr, c_double
+       type(c_ptr),value             :: h,d_psi,d_out
+       integer(c_int32_t),value      :: nterms,subtract_mean
+       integer(c_int32_t),intent(in) :: spin(*),orb_to(*),orb_from(*)
+       real(c_double),intent(in)     :: coef(*)
+       real(c_double)                :: mean(2),norm2
+     end function hxv_apply_one_body
   end interface
 
   type(c_ptr),save :: handle = c_null_ptr   !one open sector at a time (ED_HAMILTONIAN_COMMON.f90:17-18)
@@ -1057,6 +1066,46 @@ contains
     cd=0; if(create_dw)cd=1
     call check(hxv_apply_spin_pair(psi%sector,handle,cu,cd,int(nterms,c_int32_t),ou,od,cf,psi%d,out%d,norm2),"gpu_apply_spin_pair_dev")
   end subroutine gpu_apply_spin_pair_dev
+
+  !> One-body operators inside the OPEN sector (include/hxv.h, hxv_apply_one_body): the start vectors of the bond-order, current-current and
+  !! inter-orbital exciton susceptibilities,
+  !!     out = (O - m) psi,   O = sum_t coef(t) c^dagger_{ipos_to(t),s} c_{ipos_from(t),s},   s = ispin(t) (1 = up, 2 = dw),
+  !!     mean = <psi|O|psi>/<psi|psi>,   m = mean unless subtract_mean=.false.,   norm2 = <out|out>;
+  !! ipos = 1-based orbital position in the spin string, bath included, iorb+(ilat-1)*Norb for the impurity; ipos_to = ipos_from is the
+  !! occupation; 1 to 32 terms, summed in the order given.  The signs are those of two gpu_apply_ladder calls.  An empty out is allocated
+  !! on the open sector.  chi_ab then takes, per operator, gpu_sp_lanc_tridiag_probes_dev runs in the same sector and gpu_gf_from_probes
+  !! with norm = sqrt(norm2) (INTEGRATION.md section 4).  Unsplit sectors only.
+  subroutine gpu_apply_one_body_dev(psi,ispin,ipos_to,ipos_from,coef,out,mean,norm2,subtract_mean)
+    type(gpu_vector),intent(in)    :: psi
+    integer,intent(in)             :: ispin(:),ipos_to(:),ipos_from(:)
+    complex(8),intent(in)          :: coef(:)
+    type(gpu_vector),intent(inout) :: out
+    complex(8),intent(out)         :: mean
+    real(8),intent(out)            :: norm2
+    logical,intent(in),optional    :: subtract_mean
+    integer(c_int32_t)             :: sp(32),oi(32),oj(32),sub
+    real(8)                        :: cf(64),m(2)
+    integer                        :: t,nterms
+    if(.not.c_associated(handle))stop "gpu_apply_one_body_dev ERROR: Hsector NOT set"
+    if(psi%sector_id/=handle_serial.or..not.c_associated(psi%d))stop "gpu_apply_one_body_dev ERROR: the state does not belong to the open sector"
+    nterms=size(coef)
+    if(nterms<1.or.nterms>32)stop "gpu_apply_one_body_dev ERROR: 1 to 32 terms"
+    if(size(ispin)/=nterms.or.size(ipos_to)/=nterms.or.size(ipos_from)/=nterms)&
+         stop "gpu_apply_one_body_dev ERROR: ispin, ipos_to, ipos_from and coef have one entry per term"
+    if(.not.c_associated(out%d))then
+       call check(hxv_vector_alloc(handle,out%d),"gpu_apply_one_body_dev")
+       call vec_born(out,out%d,.false.)
+    endif
+    if(out%sector_id/=handle_serial)stop "gpu_apply_one_body_dev ERROR: the output does not belong to the open sector"
+    do t=1,nterms
+       sp(t)=int(ispin(t)-1,c_int32_t); oi(t)=int(ipos_to(t)-1,c_int32_t); oj(t)=int(ipos_from(t)-1,c_int32_t)
+       cf(2*t-1)=dble(coef(t)); cf(2*t)=aimag(coef(t))
+    enddo
+    sub=1; if(present(subtract_mean))then; if(.not.subtract_mean)sub=0; endif
+    m=0d0
+    call check(hxv_apply_one_body(handle,int(nterms,c_int32_t),sp,oi,oj,cf,sub,psi%d,out%d,m,norm2),"gpu_apply_one_body_dev")
+    mean=cmplx(m(1),m(2),8)
+  end subroutine gpu_apply_one_body_dev
 
   !> the vector in the reference's host layout (this rank's slab), when it is wanted there after all (e.g. state_list of ED_DIAG)
   subroutine gpu_vector_to_host(vect,v)

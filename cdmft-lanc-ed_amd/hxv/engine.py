@@ -51,6 +51,7 @@ EXPORTS = [
     "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
     "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_reduced_dm_elems", "hxv_reduced_dm_accumulate", "hxv_twin_vector", "hxv_twin_split_plan",
     "hxv_lanczos_tridiag_probes", "hxv_gf_from_probes", "hxv_apply_density_ops", "hxv_lanczos_tridiag_pair_probes", "hxv_apply_spin_pair",
+    "hxv_apply_one_body",
 ]
 
 _lib = None
@@ -174,6 +175,7 @@ def load_library():
     L.hxv_gf_from_probes.argtypes = [i32, pd, pd, i32, pd, dbl, pd, pd]
     L.hxv_apply_density_ops.argtypes = [vp, i32, pd, i32, vp, C.POINTER(vp), pd, pd]
     L.hxv_apply_spin_pair.argtypes = [vp, vp, i32, i32, i32, pi32, pi32, pd, vp, vp, pd]
+    L.hxv_apply_one_body.argtypes = [vp, i32, pi32, pi32, pi32, pd, i32, vp, vp, pd, pd]
     _lib = L
     return L
 
@@ -1085,6 +1087,34 @@ class HxvSector:
                                                 C.cast(cf.ctypes.data, C.POINTER(C.c_double)), psi.data_ptr(), out.data_ptr(), C.byref(n2)),
              "hxv_apply_spin_pair")
         return out, n2.value
+
+    def apply_one_body(self, terms, psi, subtract_mean: bool = True, out=None):
+        """hxv_apply_one_body (include/hxv.h): out = (O - m) psi inside this sector for O = sum_t coef_t c^dagger_{i_t s_t} c_{j_t s_t}, the
+        particle-conserving same-spin bilinears (bond, current and exciton operators: hxv.observables.one_body_terms), m = <O> when
+        subtract_mean, else 0.  terms: a sequence of (spin, i, j, coef), spin 0 = up, 1 = dw, orbitals 0-based in [0, Ns) with the bath
+        included, i == j allowed; 1 to 32 of them, summed in the order given; the sign convention is that of two apply_ladder calls.  psi: a
+        device vector of this sector in the padded layout (localElems complex128 elements); out: another one, allocated when not given;
+        every element is written.  Unsplit sectors only.
+        -> (out, mean = <psi|O|psi> / <psi|psi> complex, norm2 = <out|out>)."""
+        import torch
+
+        if not (torch.is_tensor(psi) and psi.is_cuda and psi.dtype == torch.complex128 and psi.is_contiguous() and psi.numel() == self.localElems):
+            raise HxvError(f"apply_one_body takes a device vector in the padded layout (complex128, localElems = {self.localElems} elements)")
+        terms = list(terms)
+        sp = np.ascontiguousarray([t[0] for t in terms], dtype=np.int32)
+        oi = np.ascontiguousarray([t[1] for t in terms], dtype=np.int32)
+        oj = np.ascontiguousarray([t[2] for t in terms], dtype=np.int32)
+        cf = np.ascontiguousarray([complex(t[3]) for t in terms], dtype=np.complex128)
+        if out is None:
+            out = torch.empty(self.localElems, dtype=torch.complex128, device=psi.device)
+        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.complex128 and out.is_contiguous() and out.numel() == self.localElems):
+            raise HxvError("apply_one_body: out is a device vector of this sector in the padded layout")
+        torch.cuda.synchronize(psi.device)
+        mean, n2 = np.zeros(2), C.c_double()
+        _chk(load_library().hxv_apply_one_body(self._h, len(terms), _p(sp, C.c_int32), _p(oi, C.c_int32), _p(oj, C.c_int32),
+                                               C.cast(cf.ctypes.data, C.POINTER(C.c_double)), int(bool(subtract_mean)), psi.data_ptr(), out.data_ptr(),
+                                               _p(mean, C.c_double), C.byref(n2)), "hxv_apply_one_body")
+        return out, complex(mean[0], mean[1]), n2.value
 
     def time_lanczos(self, nrep: int) -> float:
         import torch

@@ -216,3 +216,119 @@ def spin_pair_susceptibility(sec, sec_lower, sec_raise, psi, e_state: float, ops
             chi[:, a, :] += greens.evaluate(poles, wts, z, e_state, -1.0)   # wts[m, b] = <O_b psi|m><m|O_a psi>
             info["nsteps_lower"][a] = n
     return chi, info
+
+
+def one_body_terms(kind, pairs=None):
+    """The operators of HxvSector.apply_one_body as a list of term lists [(spin, i, j, coef), ...], one per entry of `pairs` (orbital pairs
+    (i, j), 0-based in [0, Ns)): "hop" = sum_s c^+_is c_js, "bond" = sum_s (c^+_is c_js + h.c.), "current" = i sum_s (c^+_is c_js - h.c.),
+    "exciton_singlet" = sum_s c^+_as c_bs and "exciton_triplet_z" = sum_s s c^+_as c_bs (s = +1 up, -1 dw) for pairs (a, b) of orbitals
+    (the triplet xy component c^+_a,up c_b,dw is spin_pair_terms' kind); an explicit list of term lists is taken as it is."""
+    if isinstance(kind, str):
+        if kind not in ("hop", "bond", "current", "exciton_singlet", "exciton_triplet_z") or pairs is None:
+            raise HxvError('one_body_terms: kind is "hop", "bond", "current", "exciton_singlet" or "exciton_triplet_z" with a list of orbital '
+                           "pairs, or a list of term lists")
+        ops = []
+        for i, j in pairs:
+            i, j = int(i), int(j)
+            if kind == "bond":
+                ops.append([(s, a, b, 1.0 + 0.0j) for s in (0, 1) for a, b in ((i, j), (j, i))])
+            elif kind == "current":
+                ops.append([(s, a, b, c) for s in (0, 1) for a, b, c in ((i, j, 1.0j), (j, i, -1.0j))])
+            else:
+                ops.append([(s, i, j, complex(-1.0 if (kind == "exciton_triplet_z" and s == 1) else 1.0)) for s in (0, 1)])
+        return ops
+    return [[(int(s), int(i), int(j), complex(c)) for s, i, j, c in op] for op in kind]
+
+
+def _one_body_dagger(op):
+    return [(s, j, i, np.conj(complex(c))) for s, i, j, c in op]
+
+
+def _one_body_summed(op):
+    """a term list as {(spin, i, j): summed coefficient} without the zeros: equal for two lists that are the same operator term by term"""
+    acc = {}
+    for s, i, j, c in op:
+        acc[(s, i, j)] = acc.get((s, i, j), 0.0) + complex(c)
+    return {k: v for k, v in acc.items() if v != 0.0}
+
+
+def one_body_susceptibility(sec, psi, e_state: float, ops, z, nlanc: int = 200, cutoff: float = 1e-8):
+    """chi_ab(z) = <<dO_a; dO_b^+>> of ONE device-resident eigenstate psi (energy e_state) of the open sector `sec` for one-body operators
+    O_a = sum_t coef_t c^+_{i s} c_{j s} (HxvSector.apply_one_body; ops as one_body_terms returns them, 1 to 8), on the fluctuations
+    dO = O - <O>: spin_pair_susceptibility's formula with both neighbouring sectors equal to `sec`,
+
+        chi_ab(z) = -[ sum_n <dO_a^+ psi|n><n|dO_b^+ psi> / (z - e_n)  -  sum_m <dO_b psi|m><m|dO_a psi> / (z + e_m) ],   e = E_level - e_state.
+
+    Column b of the first sum is one lanczos_tridiag_probes run from dO_b^+ psi with all dO_a^+ psi as probes, row a of the second one run
+    from dO_a psi with all dO_b psi as probes; a start vector with norm2 < 1e-24 is skipped.  Poles with |e_n| <= cutoff are dropped and
+    their weight reported, as in greens.chi_evaluate and for its reason: a run started from dO|psi> still finds psi itself to rounding.
+    When every operator equals its own dagger as a term multiset the second set of runs is the first: one set runs and chi_evaluate sums
+    both.  Nothing Dim-sized crosses PCIe.
+    -> (chi[len(z), nops, nops] complex128, info = {"mean", "norm2", "nsteps", "dropped_weight"}; mean, norm2 and nsteps have the shape
+    (2, nops): [0] the O^+ side, [1] the O side, equal for Hermitian operators)."""
+    from . import greens
+
+    ops = one_body_terms(ops)
+    nops = len(ops)
+    if nops < 1 or nops > 8:
+        raise HxvError("one_body_susceptibility: 1 to 8 operators per call (HXV_MAX_PROBES)")
+    z = np.asarray(z, dtype=np.complex128).reshape(-1)
+    dag = [_one_body_dagger(op) for op in ops]
+    hermitian = all(_one_body_summed(a) == _one_body_summed(b) for a, b in zip(ops, dag))
+    chi = np.zeros((z.size, nops, nops), dtype=np.complex128)
+    mean, norm2 = np.zeros((2, nops), dtype=np.complex128), np.zeros((2, nops))
+    nsteps, dropped = np.zeros((2, nops), dtype=np.int64), 0.0
+    nl = min(int(nlanc), sec.Dim)
+
+    def pole_sum(poles, wts, sign):
+        e = poles - float(e_state)
+        keep = np.abs(e) > float(cutoff)
+        return greens.evaluate(poles[keep], wts[keep], z, e_state, sign), float(np.abs(wts[~keep]).sum())
+
+    for side, lists in enumerate((dag,) if hermitian else (dag, ops)):
+        vecs = [sec.apply_one_body(op, psi, subtract_mean=True) for op in lists]
+        mean[side], norm2[side] = [m for _, m, _ in vecs], [n2 for _, _, n2 in vecs]
+        for k in range(nops):
+            if vecs[k][2] < 1e-24:
+                continue
+            al, bl, ov, n = sec.lanczos_tridiag_probes(vecs[k][0], [v for v, _, _ in vecs], nl)
+            poles, wts = greens.poles_weights(al[:n], bl[:n], ov, np.sqrt(vecs[k][2]))
+            nsteps[side, k] = n
+            if hermitian:
+                chi[:, :, k], d = greens.chi_evaluate(poles, wts, z, e_state, cutoff)
+            elif side == 0:
+                part, d = pole_sum(poles, wts, +1.0)         # wts[n, a] = <dO_a^+ psi|n><n|dO_b^+ psi>, b = k
+                chi[:, :, k] -= part
+            else:
+                part, d = pole_sum(poles, wts, -1.0)         # wts[m, b] = <dO_b psi|m><m|dO_a psi>, a = k
+                chi[:, k, :] += part
+            dropped += d
+    if hermitian:
+        mean[1], norm2[1], nsteps[1] = mean[0], norm2[0], nsteps[0]
+    return chi, dict(mean=mean, norm2=norm2, nsteps=nsteps, dropped_weight=dropped)
+
+
+def one_body_density_matrix(sec, psi) -> np.ndarray:
+    """rho[s, i, j] = <psi|c^+_{i s} c_{j s}|psi> / <psi|psi> over ALL Ns orbitals of the sector, bath included (observables() covers the
+    impurity block): complex (2, Ns, Ns) from the means of 2 Ns^2 single-term apply_one_body calls.  A convenience, not a hot path."""
+    import math
+
+    import torch
+
+    # Ns from the basis maps: the n with C(n, particles) = dimension, for the spin that has particles (an empty sector of both spins has
+    # no one-body density matrix to speak of)
+    ns = 0
+    for cfgs in sec.maps():
+        npart = bin(int(cfgs[0])).count("1")
+        if npart:
+            ns = next(n for n in range(npart, 33) if math.comb(n, npart) == len(cfgs))
+            break
+    if not ns:
+        raise HxvError("one_body_density_matrix: the sector holds no particle")
+    rho =np.zeros((2, ns, ns), dtype=np.complex128)
+    out = torch.empty_like(psi)
+    for s in (0, 1):
+        for i in range(ns):
+            for j in range(ns):
+                rho[s, i, j] = sec.apply_one_body([(s, i, j, 1.0)], psi, subtract_mean=False, out=out)[1]
+    return rho

@@ -634,6 +634,43 @@ int hxv_apply_spin_pair(hxv_handle *from, hxv_handle *to, int32_t create_up, int
                         const int32_t *orb_dw, const double *coef /* [nterms] complex, interleaved */, const void *d_psi, void *d_out,
                         double *norm2);
 
+/* ---- one-body operators inside a sector: bond, current, exciton susceptibilities, one-body density matrix -----------------
+ * O = sum_t coef_t c^dagger_{i_t s_t} c_{j_t s_t}: the particle-conserving same-spin bilinears, which stay inside the handle's sector.
+ * spin 0 = up, 1 = dw; orb_to = i and orb_from = j are 0-based in [0, Ns), bath included, as in hxv_apply_ladder; i == j is allowed and
+ * is the occupation of any orbital.  The bond operator B_ij = sum_s (c^+_is c_js + h.c.), the current J_ij = i sum_s (c^+_is c_js - h.c.)
+ * and the inter-orbital excitons sum_s c^+_as c_bs (singlet), sum_s s c^+_as c_bs (triplet z) are term lists of this kind (the triplet xy
+ * component c^+_a,up c_b,dw is hxv_apply_spin_pair's).
+ *   mean  = <psi|O|psi> / <psi|psi>, complex (re, im), always returned;   d_out = (O - m) psi, m = mean when subtract_mean != 0, else 0;
+ *   *norm2 = <out|out>.  mean and norm2 may each be NULL.  Terms are summed in the order given; a repeated (spin, i, j) is allowed.
+ * SIGN: the true fermionic one, (-1)^(occupied same-spin orbitals strictly between i and j) -- the product of the signs of c_j then
+ * c^dagger_i as hxv_apply_ladder applies them; a same-spin bilinear carries no cross-spin sign.  A single term with coef = 1 and
+ * subtract_mean = 0 equals the two ladder calls through (nup-1, ndw) or (nup, ndw-1) bit for bit, except that an element no term reaches
+ * is +0 here and may be -0 there.
+ * LAYOUT: d_psi and d_out are vectors of `h` in the padded device layout; pad rows of d_psi are never read, every element of d_out is
+ * written, pad rows as exact zeros; d_out != d_psi.  DEVICE ROW ORDER: the handle's own on both sides; the up tables are by device row and
+ * carry the basis signs of source and target row, so the host result is the same bit for bit with or without an order.  A real d_psi with
+ * real coefficients gives imaginary parts that are exactly zero.
+ * One gather pass: a work item is 256 rows of one column; a dw term reads the same rows of another column (its table entry is uniform
+ * over the workgroup, a dead column skips the term), an up term gathers another row of the same column, each distinct up table looked up
+ * once per row; the first live term is stored, the others added in order; one 16-byte store per element.  <psi|psi>, <psi|out> and
+ * <out|out> ride along as per-workgroup partial sums added in a fixed order.  With subtract_mean a streaming pass computes out -= m psi
+ * and sums <out|out> afresh from what it stores (not norm2 - |m|^2 <psi|psi>, which cancels for near-eigen-operators).  No floating-point
+ * atomics, a fixed work list: the same inputs on the same handle give the same bits on every call.  Per-call scratch (the partial sums)
+ * comes from the buffer cache and is back when the call returns.  Runs on the handle's stream and returns when the scalars are on the
+ * host; nothing Dim-sized crosses PCIe.
+ * TABLES: one per distinct (spin, i, j), 4 dim_s bytes, built on first use and kept with the handle's sector image; an image keeps at most
+ * 128 of them (C3: 6.6 MB; Ns = 18 at half filling: 25 MB -- all 2 Ns^2 would be 126 MB there), the least recently used one goes first.
+ * SPLIT SECTORS ARE NOT BUILT: HXV_ERR_UNSUPPORTED when the handle has nranks > 1, decided locally and identically on every rank before
+ * any collective step (up terms are rank-local, dw terms need the exchanged vector).
+ * Errors (nothing is written): HXV_ERR_ARG for a NULL handle, vector or array, nterms outside [1, HXV_MAX_ONE_BODY_TERMS], a spin that is
+ * not 0 or 1, an orbital outside [0, Ns), a coefficient that is not finite, d_out == d_psi; HXV_ERR_STATE for handles without basis maps
+ * (from CSR, dw panels); HXV_ERR_UNSUPPORTED as above.  HXV_ERR_ARG also for a state that is zero or not finite: <psi|psi> is known only
+ * from the gather pass, so in this one case d_out has been overwritten (mean and norm2 have not).                                      */
+#define HXV_MAX_ONE_BODY_TERMS 32
+int hxv_apply_one_body(hxv_handle *h, int32_t nterms, const int32_t *spin /* 0 up, 1 dw */, const int32_t *orb_to /* i */,
+                       const int32_t *orb_from /* j */, const double *coef /* [nterms] complex, interleaved */, int32_t subtract_mean,
+                       const void *d_psi, void *d_out, double *mean /* [2] re, im */, double *norm2);
+
 /* ---- device vectors owned by the library --------------------------------------------------------------------------------
  * For host programs without a HIP binding of their own (the Fortran glue): a local vector of the handle's sector in the padded device
  * layout (hxv_localvec_elems() complex elements, zeroed), from the engine's buffer cache.  Such a pointer is what the device drivers take
