@@ -305,3 +305,17 @@ struct hxv_handle {
 };
 
 inline bool hxv::dw_part_in_pieces(const hxv_handle* h) { return h->host.exchange == 2 && h->host.nranks > 1; }
+
+namespace hxv {
+// room for `want` doubles in the handle's page-locked staging array h_probe_ov (grown on demand, never shrunk, freed with the handle): where
+// the sums of a driver's step land by a truly asynchronous copy
+inline int ensure_probe_stage(hxv_handle* h, int64_t want) {
+  if (want <= h->probe_ov_n) return HXV_OK;
+  if (h->h_probe_ov) (void)hipHostFree(h->h_probe_ov);
+  h->h_probe_ov = nullptr;
+  h->probe_ov_n = 0;
+  HIPCHK(hipHostMalloc((void**)&h->h_probe_ov, (size_t)want * sizeof(double), hipHostMallocDefault));
+  h->probe_ov_n = want;
+  return HXV_OK;
+}
+}  // namespace hxv

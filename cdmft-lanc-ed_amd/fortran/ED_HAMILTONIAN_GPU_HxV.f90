@@ -47,6 +47,9 @@ module ED_HAMILTONIAN_GPU_HXV
   public :: gpu_apply_density_ops_dev
   public :: gpu_apply_spin_pair_dev
   public :: gpu_apply_one_body_dev
+  !Chebyshev recurrence: moments and f(H) on a device-resident state (include/hxv.h: hxv_chebyshev_moments, hxv_chebyshev_apply)
+  public :: gpu_chebyshev_moments_dev
+  public :: gpu_chebyshev_apply_dev
   public :: gpu_vector_to_host
   public :: gpu_vector_from_host
   public :: gpu_free_vector
@@ -417,6 +420,23 @@ module ED_HAMILTONIAN_GPU_HXV
        real(c_double),intent(in)     :: coef(*)
        real(c_double)                :: mean(2),norm2
      end function hxv_apply_one_body
+     integer(c_int) function hxv_chebyshev_moments(h,d_vin,nprobes,d_probes,nmom,a,b,moments,self_moments) bind(C,name="hxv_chebyshev_moments")
+       import :: c_int, c_int32_t, c_ptr, c_double, c_double_complex
+       type(c_ptr),value         :: h,d_vin
+       integer(c_int32_t),value  :: nprobes,nmom
+       type(c_ptr)               :: d_probes(*)
+       real(c_double),value      :: a,b
+       complex(c_double_complex) :: moments(*)
+       real(c_double)            :: self_moments(*)
+     end function hxv_chebyshev_moments
+     integer(c_int) function hxv_chebyshev_apply(h,d_vin,ncoef,coef,a,b,d_out,norm2) bind(C,name="hxv_chebyshev_apply")
+       import :: c_int, c_int32_t, c_ptr, c_double, c_double_complex
+       type(c_ptr),value                    :: h,d_vin,d_out
+       integer(c_int32_t),value             :: ncoef
+       complex(c_double_complex),intent(in) :: coef(*)
+       real(c_double),value                 :: a,b
+       real(c_double)                       :: norm2
+     end function hxv_chebyshev_apply
   end interface
 
   type(c_ptr),save :: handle = c_null_ptr   !one open sector at a time (ED_HAMILTONIAN_COMMON.f90:17-18)
@@ -924,6 +944,67 @@ contains
     if(size(probes)>0)overlaps=ov
     if(present(nsteps))nsteps=int(ns)
   end subroutine gpu_sp_lanc_tridiag_probes_dev
+
+  !> Chebyshev moments of a device vector of the open sector (include/hxv.h, hxv_chebyshev_moments): with Ht = (H - b)/a and the spectrum
+  !! of H inside [b-a, b+a],
+  !!     moments(j,n) = <probes(j)|T_{n-1}(Ht)|vin>,  n = 1..size(moments,2),  from size(moments,2)-1 products,
+  !!     self_moments(k) = <vin|T_{k-1}(Ht)|vin>,  k = 1..2*size(moments,2)-1  (optional), from the same products.
+  !! vin is used as given (not normalised) and only read; up to 8 probes, none is allowed (moments is then (0,nmom) and only its second
+  !! extent is used).  A window that does not hold the spectrum stops the program with the engine's message ("spectrum outside the window").
+  subroutine gpu_chebyshev_moments_dev(vin,probes,a,b,moments,self_moments)
+    type(gpu_vector),intent(in)      :: vin
+    type(gpu_vector),intent(in)      :: probes(:)
+    real(8),intent(in)               :: a,b
+    complex(8),intent(inout)         :: moments(:,:)
+    real(8),intent(inout),optional   :: self_moments(:)
+    type(c_ptr)                      :: plist(8)
+    complex(8),allocatable           :: mom(:,:)
+    real(8),allocatable              :: smom(:)
+    integer                          :: j,nmom
+    if(.not.c_associated(handle))stop "gpu_chebyshev_moments_dev ERROR: Hsector NOT set"
+    if(vin%sector_id/=handle_serial.or..not.c_associated(vin%d))stop "gpu_chebyshev_moments_dev ERROR: the start vector does not belong to the open sector"
+    if(size(probes)>8)stop "gpu_chebyshev_moments_dev ERROR: more than 8 probes"
+    nmom=size(moments,2)
+    if(size(moments,1)/=size(probes).or.nmom<1)stop "gpu_chebyshev_moments_dev ERROR: moments must be (size(probes),nmom), nmom >= 1"
+    if(present(self_moments))then
+       if(size(self_moments)/=2*nmom-1)stop "gpu_chebyshev_moments_dev ERROR: self_moments must have 2*nmom-1 entries"
+    endif
+    plist=c_null_ptr
+    do j=1,size(probes)
+       if(probes(j)%sector_id/=handle_serial.or..not.c_associated(probes(j)%d))stop "gpu_chebyshev_moments_dev ERROR: a probe does not belong to the open sector"
+       plist(j)=probes(j)%d
+    enddo
+    allocate(mom(max(size(probes),1),nmom),smom(2*nmom-1))      !(contiguous, whatever section the caller passed)
+    call check(hxv_chebyshev_moments(handle,vin%d,int(size(probes),c_int32_t),plist,int(nmom,c_int32_t),a,b,mom,smom),"gpu_chebyshev_moments_dev")
+    if(size(probes)>0)moments=mom
+    if(present(self_moments))self_moments=smom
+  end subroutine gpu_chebyshev_moments_dev
+
+  !> A polynomial of H on a device vector of the open sector (include/hxv.h, hxv_chebyshev_apply):
+  !!     out = sum_{n=1}^{size(coef)} coef(n) T_{n-1}(Ht) vin,   norm2 = <out|out>,
+  !! size(coef)-1 products; coef from the series of e^{-tau H} or e^{-iHt} on the window (a,b).  vin is only read; an empty out is
+  !! allocated on the open sector; out must not be vin.
+  subroutine gpu_chebyshev_apply_dev(vin,coef,a,b,out,norm2)
+    type(gpu_vector),intent(in)    :: vin
+    complex(8),intent(in)          :: coef(:)
+    real(8),intent(in)             :: a,b
+    type(gpu_vector),intent(inout) :: out
+    real(8),intent(out),optional   :: norm2
+    complex(8),allocatable         :: cf(:)
+    real(8)                        :: n2
+    if(.not.c_associated(handle))stop "gpu_chebyshev_apply_dev ERROR: Hsector NOT set"
+    if(vin%sector_id/=handle_serial.or..not.c_associated(vin%d))stop "gpu_chebyshev_apply_dev ERROR: the start vector does not belong to the open sector"
+    if(size(coef)<1)stop "gpu_chebyshev_apply_dev ERROR: at least one coefficient"
+    if(.not.c_associated(out%d))then
+       call check(hxv_vector_alloc(handle,out%d),"gpu_chebyshev_apply_dev")
+       call vec_born(out,out%d,.false.)
+    endif
+    if(out%sector_id/=handle_serial)stop "gpu_chebyshev_apply_dev ERROR: the output does not belong to the open sector"
+    allocate(cf(size(coef))); cf=coef                           !(contiguous, whatever section the caller passed)
+    n2=0d0
+    call check(hxv_chebyshev_apply(handle,vin%d,int(size(coef),c_int32_t),cf,a,b,out%d,n2),"gpu_chebyshev_apply_dev")
+    if(present(norm2))norm2=n2
+  end subroutine gpu_chebyshev_apply_dev
 
   !> TWO gpu_sp_lanc_tridiag_probes_dev runs on one product per step (real H; include/hxv.h, hxv_lanczos_tridiag_pair_probes): the start
   !! vectors and the probes are REAL vectors of the open sector (c / c^dagger applied to a real ground state), the probes are shared by both

@@ -51,7 +51,7 @@ EXPORTS = [
     "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
     "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_reduced_dm_elems", "hxv_reduced_dm_accumulate", "hxv_twin_vector", "hxv_twin_split_plan",
     "hxv_lanczos_tridiag_probes", "hxv_gf_from_probes", "hxv_apply_density_ops", "hxv_lanczos_tridiag_pair_probes", "hxv_apply_spin_pair",
-    "hxv_apply_one_body",
+    "hxv_apply_one_body", "hxv_chebyshev_moments", "hxv_chebyshev_apply",
 ]
 
 _lib = None
@@ -176,6 +176,8 @@ def load_library():
     L.hxv_apply_density_ops.argtypes = [vp, i32, pd, i32, vp, C.POINTER(vp), pd, pd]
     L.hxv_apply_spin_pair.argtypes = [vp, vp, i32, i32, i32, pi32, pi32, pd, vp, vp, pd]
     L.hxv_apply_one_body.argtypes = [vp, i32, pi32, pi32, pi32, pd, i32, vp, vp, pd, pd]
+    L.hxv_chebyshev_moments.argtypes = [vp, vp, i32, C.POINTER(vp), i32, dbl, dbl, pd, pd]
+    L.hxv_chebyshev_apply.argtypes = [vp, vp, i32, pd, dbl, dbl, vp, pd]
     _lib = L
     return L
 
@@ -1115,6 +1117,53 @@ class HxvSector:
                                                C.cast(cf.ctypes.data, C.POINTER(C.c_double)), int(bool(subtract_mean)), psi.data_ptr(), out.data_ptr(),
                                                _p(mean, C.c_double), C.byref(n2)), "hxv_apply_one_body")
         return out, complex(mean[0], mean[1]), n2.value
+
+    # -- Chebyshev recurrence -----------------------------------------------------------------
+    def _padded(self, v, what: str) -> bool:
+        import torch
+
+        if not (torch.is_tensor(v) and v.is_cuda and v.dtype == torch.complex128 and v.is_contiguous() and v.numel() == self.localElems):
+            raise HxvError(f"{what} takes device vectors in the padded layout (complex128, localElems = {self.localElems} elements); "
+                           "use pad() / vector_from_host() for a vector in the reference's layout")
+        return True
+
+    def chebyshev_moments(self, vin, probes, nmom: int, a: float, b: float):
+        """hxv_chebyshev_moments (include/hxv.h): the Chebyshev vectors t_n = T_n((H - b)/a) vin for n < nmom, from nmom - 1 products, with
+        their overlaps with the probes.  The spectrum of H must lie inside [b - a, b + a] (hxv.chebyshev.spectral_window); the driver's
+        guard raises HxvError when it does not.  vin (used as given, not normalised, not modified) and every probe are device vectors of
+        this sector in the padded layout (this rank's slab on a split sector, collective there); at most 8 probes, none is allowed.
+        -> (moments[nmom, nprobes] complex128 = <p_j|t_n>, self_moments[2*nmom - 1] = <vin|T_k|vin>)."""
+        import torch
+
+        probes = list(probes)
+        for v in [vin] + probes:
+            self._padded(v, "chebyshev_moments")
+        torch.cuda.synchronize(vin.device)
+        npr = len(probes)
+        mom = np.zeros((max(nmom, 0), npr), dtype=np.complex128)
+        smom = np.zeros(max(2 * nmom - 1, 1))
+        plist = (C.c_void_p * max(npr, 1))(*[p.data_ptr() for p in probes])
+        _chk(load_library().hxv_chebyshev_moments(self._h, vin.data_ptr(), npr, plist if npr else None, nmom, a, b,
+                                                  C.cast(mom.ctypes.data, C.POINTER(C.c_double)) if npr else None, _p(smom, C.c_double)),
+             "hxv_chebyshev_moments")
+        return mom, smom
+
+    def chebyshev_apply(self, vin, coef, a: float, b: float, out=None):
+        """hxv_chebyshev_apply (include/hxv.h): out = sum_n coef[n] T_n((H - b)/a) vin, len(coef) - 1 products; coef complex
+        (hxv.chebyshev.exp_coefficients for e^{-tau H}, propagator_coefficients for e^{-iHt}).  vin: a device vector of this sector in the
+        padded layout, not modified; out: another one, allocated when not given.  -> (out, norm2 = <out|out>)."""
+        import torch
+
+        self._padded(vin, "chebyshev_apply")
+        cf = np.ascontiguousarray(np.atleast_1d(coef), dtype=np.complex128)
+        if out is None:
+            out = torch.empty(self.localElems, dtype=torch.complex128, device=vin.device)
+        self._padded(out, "chebyshev_apply")
+        torch.cuda.synchronize(vin.device)
+        n2 = C.c_double()
+        _chk(load_library().hxv_chebyshev_apply(self._h, vin.data_ptr(), cf.size, C.cast(cf.ctypes.data, C.POINTER(C.c_double)), a, b,
+                                                out.data_ptr(), C.byref(n2)), "hxv_chebyshev_apply")
+        return out, n2.value
 
     def time_lanczos(self, nrep: int) -> float:
         import torch

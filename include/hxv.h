@@ -393,6 +393,44 @@ int hxv_lanczos_tridiag_pair_probes(hxv_handle *h, const void *d_vin_a, const vo
 int hxv_gf_from_probes(int32_t nsteps, const double *alanc, const double *blanc, int32_t nprobes, const double *overlaps,
                        double norm /* |v| of the unnormalised start vector */, double *poles /* [nsteps] */,
                        double *weights /* [nsteps][nprobes] complex */);
+/* ---- CHEBYSHEV RECURRENCE: functions of H applied to a device-resident state, and spectral moments with a uniform resolution.  With the
+ * window  Ht = (H - b)/a,  spectrum of H inside [b - a, b + a]  (hxv.chebyshev.spectral_window gives one), the vectors
+ *     t_0 = v,   t_1 = Ht v,   t_{n+1} = 2 Ht t_n - t_{n-1}      (t_n = T_n(Ht) v)
+ * carry every polynomial of H: e^{-tau H} v (thermal typical states), e^{-iHt} v (real-time propagation), spectral filters, and the moments
+ * of the kernel polynomial method.  Per order: ONE product (the engine's own, through the slab product without an epilogue) and ONE fused
+ * streaming pass that forms t_{n+1} over t_{n-1}, adds c_{n+1} t_{n+1} to the running sum, and reduces the overlaps with the probes together
+ * with <t_{n+1}|t_{n+1}> and <t_{n+1}|t_n>; (3 + M)*16 bytes per state for M probes, (4 + M)*16 with a running sum.  No floating-point
+ * atomics: the same vectors on the same handle give the same bits on every call.  COMPLEX VECTORS ONLY: a real-vector form is not provided,
+ * option "real_vectors" does not apply.
+ * hxv_chebyshev_moments:
+ *   moments[2*(n*nprobes + j)], [.. + 1] = Re, Im <p_j|T_n(Ht)|v> = sum conj(p_j[i]) t_n[i]  for n < nmom, from nmom - 1 products.  d_probes as
+ *     in hxv_lanczos_tridiag_probes (used as given; a probe may be d_vin itself); nprobes = 0: d_probes and moments may be NULL.
+ *   self_moments[k] = <v|T_k(Ht)|v> for k <= 2*nmom - 2, from the same products:  mu_0 = <v|v>,  mu_1 = Re<t_1|t_0>,
+ *     mu_{2n} = 2<t_n|t_n> - mu_0,  mu_{2n+1} = 2 Re<t_{n+1}|t_n> - mu_1.  May be NULL.
+ *   d_vin is used as given, NOT normalised, and only read.
+ * hxv_chebyshev_apply:
+ *   d_out = sum_{n < ncoef} coef_n T_n(Ht) v,  coef[2n], [2n+1] = Re, Im coef_n (hxv.chebyshev.exp_coefficients / propagator_coefficients);
+ *   *norm2 = <d_out|d_out> (may be NULL).  d_vin is only read; d_out == d_vin is refused.  ncoef - 1 products.
+ * SCRATCH: three vector-sized blocks and one small one from the device-buffer cache, back there on every way out ("pool_live_blocks").
+ * WINDOW GUARD: for a spectrum inside the window |t_n| <= |v|.  After EVERY order the driver compares <t_n|t_n> with 4 <v|v> and returns
+ * HXV_ERR_ARG ("spectrum outside the window") when it is larger or when any sum of the order is not finite; 4 is a guard, not a tolerance -- a
+ * window that is too narrow grows geometrically and passes it within a few orders.  The sums are read with ONE stream synchronisation per
+ * order, on split and unsplit sectors alike (it also delivers the moments): the host's launch latency of the next product, a few tens of
+ * microseconds, is exposed once per order.  After such an error d_out holds the partial sum of the orders before it.
+ * No basis maps are needed: handles from hxv_create_from_csr, with the spH0nd block, with either job_up work alike.
+ * SPLIT SECTORS: this rank's slab, collective; all 2*nprobes + 3 sums of an order in ONE all-reduce, so every rank sees the same sums and
+ * all ranks leave together on the guard; argument and allocation failures are agreed on by all ranks before the first collective step.  d_vin
+ * is copied before the first exchange, so a start vector at hxv_slab_home is staged (the exchange then overwrites that place); a PROBE or
+ * d_out inside one of the handle's gather buffers is refused on every rank together, as in hxv_lanczos_tridiag_probes.  The vectors of the
+ * recurrence live in cache blocks, not in the gather buffers: one slab copy per product.
+ * Errors: HXV_ERR_ARG for a NULL handle, d_vin, d_out or coef, nmom < 1, ncoef < 1, a <= 0, a non-finite a, b or coefficient, nprobes outside
+ * [0, HXV_MAX_PROBES], nprobes > 0 with a NULL list, a NULL entry or NULL moments, a zero or non-finite start vector, a probe whose overlap with the start vector is not finite, and from the
+ * guard. */
+int hxv_chebyshev_moments(hxv_handle *h, const void *d_vin, int32_t nprobes, const void *const *d_probes, int32_t nmom, double a, double b,
+                          double *moments /* [nmom][nprobes] complex, order-major; NULL iff nprobes == 0 */,
+                          double *self_moments /* [2*nmom-1] real, may be NULL */);
+int hxv_chebyshev_apply(hxv_handle *h, const void *d_vin, int32_t ncoef, const double *coef /* [ncoef] complex */, double a, double b,
+                        void *d_out, double *norm2 /* <out|out>, may be NULL */);
 /* ---- Several lowest eigenpairs on device: the call SciFortran's sp_eigh (P-ARPACK) serves at ED_DIAG.f90:152-160,
  *   call sp_eigh(spHtimesV_p, eig_values(Neigen), eig_basis(vecDim,Neigen), Nblock, Nitermax, tol=lanc_tolerance)
  * as a thick-restart Lanczos (the explicit-restart form of ARPACK's implicitly restarted Lanczos for Hermitian
