@@ -77,6 +77,43 @@ def test_record_in_the_default_device_row_order_at_dimup_12870(built):
     assert _record_matches(m, [(8, 2), (2, 8)], seed=5) >= 1
 
 
+OTHER_NIMP = {1: (lambda M: M.hm_1dchain(Nlat=1, Nbath=3), [(2, 2), (2, 0)]),
+              3: (lambda M: M.hm_1dchain(Nlat=3, Nbath=1), [(3, 2), (3, 6)]),
+              5: (lambda M: M.hm_1dchain(Nlat=5, Nbath=1), [(5, 4), (5, 0)]),
+              8: (lambda M: M.bhz_2d(Nbath=0, Ust=0.3, Jh=0.1), [(4, 3), (4, 8)]),
+              10: (lambda M: M.hm_1dchain(Nlat=10, Nbath=0), [(5, 4)])}
+
+
+@pytest.mark.parametrize("row_order", ["off", "forced"])
+@pytest.mark.parametrize("nimp", sorted(OTHER_NIMP))
+def test_record_at_other_impurity_sizes(built, nimp, row_order, monkeypatch):
+    """Nimp in {1, 3, 5, 8, 10}: fewer W bins than waves, pair counts that are no multiple of four, both lookup widths of o >> nimp, the whole
+    LDS array of the dw pass; with each of the first four one sector with DimDw = 1.  In the reference's row order, and with the device row
+    order forced by the hooks of tests/test_gpu_row_order.py: with Ns - 1 block bits the last impurity orbital and the last bath orbital but
+    one are tied to the one high orbital, so the chains with a bath get a row order (asserted); the open 10-site chain has no orbital to move, and for the bath-less
+    BHZ cluster the order is not asserted."""
+    import hxv
+    from hxv import models
+
+    make, sectors = OTHER_NIMP[nimp]
+    m = make(models)
+    assert m.Nlat * m.Norb == nimp
+    if row_order == "off":
+        monkeypatch.setenv("HXV_ROW_ORDER", "0")
+    else:
+        monkeypatch.setenv("HXV_ROW_ORDER_MIN_DIMUP", "4")
+        monkeypatch.setenv("HXV_ROW_ORDER_BITS", str(m.Ns - 1))
+    hxv.sector_cache_clear()
+    try:
+        n = _record_matches(m, sectors, seed=300 + nimp)
+        if row_order == "off":
+            assert n == 0
+        elif nimp in (1, 3, 5):
+            assert n == len(sectors), n
+    finally:
+        hxv.sector_cache_clear()
+
+
 @pytest.mark.parametrize("kind", ["bhz", "jxjp"])
 def test_record_complex_and_spin_exchange_models(built, kind):
     from hxv import models
