@@ -14,16 +14,7 @@
 using namespace hxv;
 
 #include "hxv_call_scope.hpp"
-
-namespace hxv {
-namespace {
-thread_local std::string g_err;
-}
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-}  // namespace hxv
+#include "hxv_options.hpp"
 
 namespace hxv {
 int ensure_wt(hxv_handle* h) {
@@ -231,7 +222,6 @@ int pitch_real_of(const hxv_handle* h) { return (h->host.dimup + 15) & ~15; }
 
 extern "C" {
 
-const char* hxv_last_error(void) { return g_err.c_str(); }
 const char* hxv_version(void) { return "hxv-mi355x 0.1 (gfx950)"; }
 
 int hxv_create_from_model(const hxv_model* model, int32_t nup, int32_t ndw, int32_t rank, int32_t nranks, int32_t device,
@@ -686,120 +676,12 @@ int hxv_get_diag(const hxv_handle* h, double* diag) {
 }
 
 int hxv_set_option(hxv_handle* h, const char* name, int64_t value) {
-  if (!h || !name) return fail(HXV_ERR_ARG, "hxv_set_option: NULL");
-  // timing experiments (results are wrong or partial when set): only with HXV_EXPERIMENTS=1 in the environment
-  if (!strcmp(name, "debug") || !strcmp(name, "passes") || !strcmp(name, "job_debug")) {
-    const char* ex = getenv("HXV_EXPERIMENTS");
-    if (!(ex && ex[0] == '1') && value != (!strcmp(name, "passes") ? 3 : 0))
-      return fail(HXV_ERR_ARG, std::string("option ") + name + " is a timing experiment that gives wrong results; set HXV_EXPERIMENTS=1 to enable it");
-  }
-  if (!strcmp(name, "kernel")) {
-    if (value < 0 || value > 1) return fail(HXV_ERR_ARG, "kernel must be 0 or 1");
-    h->kernel = (int)value;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "lds_min_kb_up") || !strcmp(name, "lds_min_kb_dw")) {
-    if (value < 0 || value > 160) return fail(HXV_ERR_ARG, "lds_min_kb must be in [0,160]");
-    (name[11] == 'u' ? h->plan.opt.lds_min_kb_up : h->plan.opt.lds_min_kb_dw) = (int)value;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "lanczos_fused")) {
-    h->lz_fused = value ? 1 : 0;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "real_vectors")) {
-    h->real_vectors = value ? 1 : 0;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "lanczos_graph")) {
-    h->lz_graph = value ? 1 : 0;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "eigh_keep_pct")) {
-    if (value < 5 || value > 80) return fail(HXV_ERR_ARG, "eigh_keep_pct must be in [5,80]");
-    h->eigh_keep_pct = (int)value;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "eigh_degenerate")) {
-    h->eigh_degenerate = value ? 1 : 0;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "eigh_fuse_restart")) {
-    h->eigh_fuse_restart = value ? 1 : 0;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "eigh_measure_all")) {
-    h->eigh_measure_all = value ? 1 : 0;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "debug")) {
-    h->plan.opt.debug = (int)value;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "job_debug")) {
-    h->plan.opt.job_debug = (int)value;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "pair_rows")) {
-    if (value < -1 || value > 1) return fail(HXV_ERR_ARG, "pair_rows must be -1, 0 or 1");
-    h->plan.opt.pair_rows = (int)value;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "real_dw_pairs")) {
-    h->plan.opt.real_dw_pairs = value ? 1 : 0;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "wt_colmajor")) {
-    h->plan.opt.wt_colmajor = value ? 1 : 0;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "block_order")) {
-    if (value < -1 || value > 2) return fail(HXV_ERR_ARG, "block_order must be -1, 0, 1 or 2");
-    h->plan.opt.block_order = (int)value;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "job_max_blocks")) {
-    h->plan.opt.job_max_blocks = (int)value;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "passes")) {
-    if (value < 1 || value > 3) return fail(HXV_ERR_ARG, "passes must be 1, 2 or 3");
-    h->plan.opt.passes = (int)value;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "lanczos_inplace")) {  // split sectors: Lanczos vectors in their slot of a gather buffer (no slab copy per product)
-    h->lz_inplace = value ? 1 : 0;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "exchange_overlap")) {  // exchange mode 2: diagonal + up hops on a second stream during the transposes (plain products)
-    h->a2a_overlap = value ? 1 : 0;
-    return HXV_OK;
-  }
-  if (!strcmp(name, "fold_nd")) {  // spH0nd inside pass A (default) or as its own pass over hv
-    h->dev.nd.fold = value ? 1 : 0;  // (the handle's copy: the host description may be shared with other handles)
-    return HXV_OK;
-  }
-  // tiling knobs: rebuild the plan (old tables stay allocated until hxv_destroy)
-  TileOptions o = h->plan.opt;
-  if (!strcmp(name, "cols_per_tile")) o.cols_per_tile = (int)value;
-  else if (!strcmp(name, "rows_per_tile")) o.rows_per_tile = (int)value;
-  else if (!strcmp(name, "lds_budget_kb")) o.lds_budget_kb_up = o.lds_budget_kb_dw = (int)value;
-  else if (!strcmp(name, "lds_budget_kb_up")) o.lds_budget_kb_up = (int)value;
-  else if (!strcmp(name, "lds_budget_kb_dw")) o.lds_budget_kb_dw = (int)value;
-  else if (!strcmp(name, "tile_bits_up")) o.force_bits_up = (int)value;
-  else if (!strcmp(name, "tile_bits_dw")) o.force_bits_dw = (int)value;
-  else if (!strcmp(name, "threads_up")) o.threads_up = (int)value;
-  else if (!strcmp(name, "threads_dw")) o.threads_dw = (int)value;
-
-  else if (!strcmp(name, "sort_mode")) o.sort_mode = (int)value;
-  else if (!strcmp(name, "wt_cols")) o.wt_cols = (int)value;
-  else if (!strcmp(name, "sort_mode_dw")) o.sort_mode_dw = (int)value;
-  else if (!strcmp(name, "spread_banks")) o.spread_banks = value ? 1 : 0;
-  else if (!strcmp(name, "job_up")) o.job_up = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
-  else if (!strcmp(name, "job_cols")) o.job_cols = (int)value;
-  else if (!strcmp(name, "job_groups")) o.job_groups = (int)value;
-  else if (!strcmp(name, "job_stages")) o.job_stages = (int)value;
-  else return fail(HXV_ERR_ARG, std::string("unknown option ") + name);
+  // names, gate, ranges and where a value lives: hxv_options.cpp.  Here only what needs the device: a tiling knob rebuilds the plan
+  // (old tables stay allocated until hxv_destroy)
+  TileOptions o;
+  bool rebuild = false;
+  if (int rc = option_store(h, name, value, &o, &rebuild)) return rc;
+  if (!rebuild) return HXV_OK;
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
   TilePlan np;
@@ -823,99 +705,7 @@ int hxv_set_option(hxv_handle* h, const char* name, int64_t value) {
   return HXV_OK;
 }
 
-int64_t hxv_get_option(const hxv_handle* h, const char* name) {
-  if (!h || !name) return -1;
-  if (!strcmp(name, "real_vectors")) return h->real_vectors;
-  // what THIS open cost, microseconds (0 for the parts a cached image saved): host description, tile plan, table upload, whole create call
-  if (!strcmp(name, "open_us_host")) return (int64_t)h->open_us[0];
-  if (!strcmp(name, "open_us_plan")) return (int64_t)h->open_us[1];
-  if (!strcmp(name, "open_us_upload")) return (int64_t)h->open_us[2];
-  if (!strcmp(name, "open_us_total")) return (int64_t)h->open_us[3];
-  if (!strcmp(name, "open_cache_hit")) return h->open_cache_hit;
-  if (!strcmp(name, "lanczos_graph")) return h->lz_graph;
-  if (!strcmp(name, "eigh_degenerate")) return h->eigh_degenerate;
-  if (!strcmp(name, "eigh_fuse_restart")) return h->eigh_fuse_restart;
-  if (!strcmp(name, "eigh_keep_pct")) return h->eigh_keep_pct;
-  if (!strcmp(name, "eigh_measure_all")) return h->eigh_measure_all;
-  if (!strcmp(name, "eigh_last_full_passes")) return h->eigh_last_full;
-  if (!strcmp(name, "eigh_last_local_passes")) return h->eigh_last_local;
-  if (!strcmp(name, "eigh_last_search_products")) return h->eigh_last_search;  // *nmatvec of the last hxv_eigh_lowest = search + check
-  if (!strcmp(name, "eigh_last_check_products")) return h->eigh_last_check;
-  if (!strcmp(name, "eigh_last_restarts")) return h->eigh_last_restarts;              // thick restarts of the search round
-  if (!strcmp(name, "eigh_last_fused_restarts")) return h->eigh_last_fused_restarts;  // ... whose rotation went through tr_rotate_dots
-  if (!strcmp(name, "eigh_last_fused_first_steps")) return h->eigh_last_fused_first;  // restart cycles begun by tr_axpy_mdot
-  if (!strcmp(name, "lanczos_real_last")) return h->last_real;
-  if (!strcmp(name, "pass_b_order_last")) return h->plan.dw_order_last;  // phase order the last pass-B launch ran (0 / 1; -1: none yet)
-  if (!strcmp(name, "allreduce_count")) return h->n_allreduce;  // sum all-reduces of a split sector since creation (the drivers' dot products)
-  if (!strcmp(name, "pool_live_blocks")) return pool_live_blocks(h->device);  // buffer-cache blocks out on the handle's device (every handle's and call's)
-  if (!strcmp(name, "slab_copies")) return h->n_slab_copy;  // exchanges whose vector was not at home in a gather buffer
-  if (!strcmp(name, "lanczos_inplace")) return h->lz_inplace;
-  if (!strcmp(name, "exchange_overlap")) return h->a2a_overlap;
-  if (!strcmp(name, "kernel")) return h->kernel;
-  if (!strcmp(name, "time_kernels_overlapped_us")) return h->last_overlapped_us;
-  // the last split hxv_twin_vector INTO this handle, by HIP events on its stream (-1: none yet): pack kernel, exchange, unpack kernel
-  if (!strcmp(name, "twin_last_pack_us")) return h->twin_last_us[0];
-  if (!strcmp(name, "twin_last_exchange_us")) return h->twin_last_us[1];
-  if (!strcmp(name, "twin_last_unpack_us")) return h->twin_last_us[2];
-  if (!strcmp(name, "tile_bits_up")) return h->plan.up.lowbits;
-  if (!strcmp(name, "tile_bits_dw")) return h->plan.dw.lowbits;
-  if (!strcmp(name, "real_dw_pairs")) return h->plan.opt.real_dw_pairs;
-  if (!strcmp(name, "wt_colmajor")) return h->plan.opt.wt_colmajor;
-  if (!strcmp(name, "cols_per_tile")) return h->plan.opt.cols_per_tile;
-  if (!strcmp(name, "rows_per_tile")) return h->plan.opt.rows_per_tile;
-  if (!strcmp(name, "p16_bits_up")) return h->plan.up.p16_bits;
-  if (!strcmp(name, "p16_bits_dw")) return h->plan.dw.p16_bits;
-  if (!strcmp(name, "lds_budget_kb_up")) return h->plan.opt.lds_budget_kb_up;
-  if (!strcmp(name, "lds_budget_kb_dw")) return h->plan.opt.lds_budget_kb_dw;
-  // the remaining options a caller can set, as hxv_set_option stored them
-  if (!strcmp(name, "threads_up")) return h->plan.opt.threads_up;
-  if (!strcmp(name, "threads_dw")) return h->plan.opt.threads_dw;
-  if (!strcmp(name, "sort_mode")) return h->plan.opt.sort_mode;
-  if (!strcmp(name, "sort_mode_dw")) return h->plan.opt.sort_mode_dw;
-  if (!strcmp(name, "wt_cols")) return h->plan.opt.wt_cols;
-  if (!strcmp(name, "spread_banks")) return h->plan.opt.spread_banks;
-  if (!strcmp(name, "job_cols")) return h->plan.opt.job_cols;
-  if (!strcmp(name, "job_groups")) return h->plan.opt.job_groups;
-  if (!strcmp(name, "job_stages")) return h->plan.opt.job_stages;
-  if (!strcmp(name, "job_max_blocks")) return h->plan.opt.job_max_blocks;
-  if (!strcmp(name, "pair_rows")) return h->plan.opt.pair_rows;
-  if (!strcmp(name, "block_order")) return h->plan.opt.block_order;
-  if (!strcmp(name, "lds_min_kb_up")) return h->plan.opt.lds_min_kb_up;
-  if (!strcmp(name, "lds_min_kb_dw")) return h->plan.opt.lds_min_kb_dw;
-  if (!strcmp(name, "fold_nd")) return h->dev.nd.fold;
-  if (!strcmp(name, "lanczos_fused")) return h->lz_fused;
-  if (!strcmp(name, "k_in_up")) return h->plan.up.k_in;
-  if (!strcmp(name, "k_out_up")) return h->plan.up.k_out;
-  if (!strcmp(name, "k_in_dw")) return h->plan.dw.k_in;
-  if (!strcmp(name, "k_out_dw")) return h->plan.dw.k_out;
-  if (!strcmp(name, "n_in_up")) return h->plan.up.n_in;
-  if (!strcmp(name, "n_out_up")) return h->plan.up.n_out;
-  if (!strcmp(name, "n_in_dw")) return h->plan.dw.n_in;
-  if (!strcmp(name, "n_out_dw")) return h->plan.dw.n_out;
-  if (!strcmp(name, "slots_in_up_x100")) return (int64_t)(100 * h->plan.up.slots_in);
-  if (!strcmp(name, "slots_out_up_x100")) return (int64_t)(100 * h->plan.up.slots_out);
-  if (!strcmp(name, "slots_in_dw_x100")) return (int64_t)(100 * h->plan.dw.slots_in);
-  if (!strcmp(name, "bh_up_x100")) return (int64_t)(100 * h->plan.up.bh_per_row);
-  if (!strcmp(name, "rs_up_x100")) return (int64_t)(100 * h->plan.up.rs_per_row);
-  if (!strcmp(name, "bh_dw_x100")) return (int64_t)(100 * h->plan.dw.bh_per_row);
-  if (!strcmp(name, "rs_dw_x100")) return (int64_t)(100 * h->plan.dw.rs_per_row);
-  if (!strcmp(name, "max_block_up")) return h->plan.up.max_block;
-  if (!strcmp(name, "ncoef_up")) return h->plan.ncoef_up;  // distinct hopping amplitudes: the kernels' coefficient tables hold 2 * ncoef + 1 words
-  if (!strcmp(name, "ncoef_dw")) return h->plan.ncoef_dw;
-  if (!strcmp(name, "max_block_dw")) return h->plan.dw.max_block;
-  if (!strcmp(name, "nblocks_up")) return h->plan.up.nblocks;
-  if (!strcmp(name, "table_classes_up")) return h->plan.up.table_classes;
-  if (!strcmp(name, "table_classes_dw")) return h->plan.dw.table_classes;
-  if (!strcmp(name, "rs_tables_up")) return h->plan.up.rs_tables;
-  if (!strcmp(name, "rs_tables_dw")) return h->plan.dw.rs_tables;
-  if (!strcmp(name, "nblocks_dw")) return h->plan.dw.nblocks;
-  if (!strcmp(name, "job_up")) return h->plan.opt.job_up;
-  if (!strcmp(name, "job_up_active"))
-    return (h->plan.opt.job_up == 1 && job_up_planned(h->dev, h->plan, false, std::max(h->plan.opt.job_cols, h->plan.opt.wt_cols))) ? 1 : 0;
-  if (!strcmp(name, "max_outer_up")) return h->plan.up.max_outer;
-  if (!strcmp(name, "max_outer_dw")) return h->plan.dw.max_outer;
-  return -1;
-}
+int64_t hxv_get_option(const hxv_handle* h, const char* name) { return option_read(h, name); }
 
 int hxv_get_stats(const hxv_handle* h, hxv_stats* out) {
   if (!h || !out) return fail(HXV_ERR_ARG, "hxv_get_stats: NULL");
