@@ -1,4 +1,5 @@
-// The two host routines of hxv_eigh_lowest (hxv_eigh.hip): the dense eigensolver of the projected matrix and the restart's keep rule.
+// The host routines of hxv_eigh_lowest (hxv_eigh.hip): the dense eigensolver of the projected matrix, the restart's keep rule and the
+// orthogonality estimate that decides when the whole basis is cleaned.
 // Pure C++17, no HIP include: tests/host/eigh_small_check.cpp builds this file with a host compiler (and its sanitizers) alone.
 #pragma once
 
@@ -72,5 +73,64 @@ int keep_count(int m, int neigen, int nconv, int pct) {
   int k = neigen + std::min(nconv, (m - neigen) / 2) + std::max(1, (m - neigen) * pct / 100);
   return std::max(1, std::min(k, m - 1));
 }
+
+// Partial re-orthogonalisation (Simon 1984) in its thick-restart form: the loss of orthogonality of the next Lanczos vector against
+// every earlier basis vector is ESTIMATED from the recurrence the exact quantities obey (<q_j, v_b>: prev = step j-1, cur = step j,
+// next = step j+1, indexed by the ABSOLUTE basis slot b), so the whole basis is only touched when an estimate says so.  The active
+// basis starts at slot nlock; T is its projected matrix (column-major ma x ma), whose first k rows are the kept Ritz pairs
+// (theta_keep) with their arrow (s_keep).
+struct OmegaEstimate {
+  static constexpr double EPS = 2.220446049250313e-16;
+  std::vector<double> prev, cur, next;
+  explicit OmegaEstimate(int size = 0) : prev(size, EPS), cur(size, EPS), next(size, EPS) {}
+  // a restart: the new cycle's estimates start from rounding level (next is written before it is read)
+  void reset() {
+    std::fill(prev.begin(), prev.end(), EPS);
+    std::fill(cur.begin(), cur.end(), EPS);
+  }
+  // the rounding level of a step's estimates: |T|'s diagonal up to row j against the new vector's length
+  static double noise_level(const std::vector<double>& T, int ma, int j, double nrm) {
+    double tsc = 1.0;
+    for (int a = 0; a <= j; ++a) tsc = std::max(tsc, std::fabs(T[a + (size_t)a * ma]));
+    return 2.0 * EPS * tsc / std::max(nrm, 1e-300);
+  }
+  // the new vector was measured against slots 0..jt and those projections removed: orthogonal to rounding
+  void cleaned(int jt, double noise) { std::fill_n(next.begin(), jt + 1, noise); }
+  // step j of the active basis (slot jt = nlock + j) took the two local projections only; nrm = the new vector's length.
+  // Returns the largest estimate among the slots b < jt - 1 that the step did not touch.
+  double local_step(const std::vector<double>& T, int ma, int nlock, int k, int j, const std::vector<double>& theta_keep,
+                    const std::vector<double>& s_keep, double noise, double nrm) {
+    const int jt = nlock + j;
+    auto t_at = [&](int a, int b) { return T[a + (size_t)b * ma]; };
+    auto omc = [&](int x) -> double { return x == jt ? 1.0 : (x == jt - 1 ? noise : cur[x]); };
+    const double alpha_j = t_at(j, j), beta_j = j > k ? t_at(j, j - 1) : 0.0;
+    double maxom = 0.0;
+    for (int b = 0; b < jt - 1; ++b) {
+      if (b < nlock) {
+        next[b] = noise;  // measured and removed at every step (gs_local)
+        continue;
+      }
+      const int l = b - nlock;
+      double at;
+      if (l < k) {
+        at = theta_keep[l] * cur[b] + s_keep[l] * omc(nlock + k);
+      } else {
+        at = t_at(l, l) * cur[b] + t_at(l + 1, l) * omc(b + 1);
+        if (l > k)
+          at += t_at(l, l - 1) * omc(b - 1);
+        else
+          for (int i2 = 0; i2 < k; ++i2) at += s_keep[i2] * omc(nlock + i2);
+      }
+      double val = (at - alpha_j * cur[b] - beta_j * prev[b]) / std::max(nrm, 1e-300);
+      val += std::copysign(noise, val);
+      next[b] = val;
+      maxom = std::max(maxom, std::fabs(val));
+    }
+    next[jt - 1 < 0 ? 0 : jt - 1] = noise;
+    next[jt] = noise;
+    return maxom;
+  }
+  void advance() { prev.swap(cur), cur.swap(next); }  // the step is taken: j becomes j + 1
+};
 
 }  // namespace

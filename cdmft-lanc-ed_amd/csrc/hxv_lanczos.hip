@@ -412,15 +412,7 @@ int tridiag_run(hxv_handle* h, const char* who, int rc_args, const void* d_vin, 
     n_part = (size_t)2 * nprobes * RED_BLOCKS;
     HIPCHK(pooled.take((n_chk + n_part + 2 * nprobes) * sizeof(double), &d_ws));
     // page-locked staging for the overlaps of every step: a copy into the caller's pageable array could make the runtime wait per step
-    const int64_t want = (int64_t)2 * nprobes * nlanc;
-    if (want > h->probe_ov_n) {
-      if (h->h_probe_ov) (void)hipHostFree(h->h_probe_ov);
-      h->h_probe_ov = nullptr;
-      h->probe_ov_n = 0;
-      HIPCHK(hipHostMalloc((void**)&h->h_probe_ov, (size_t)want * sizeof(double), hipHostMallocDefault));
-      h->probe_ov_n = want;
-    }
-    return HXV_OK;
+    return ensure_probe_stage(h, (int64_t)2 * nprobes * nlanc);
   };
   if (int rca = comm_agree(h, resources())) return rca;
   if (int rcc = need_comm(h, "device Lanczos")) return rcc;
@@ -731,15 +723,7 @@ int tridiag_pair_run(hxv_handle* h, const char* who, int rc_args, const void* d_
     HIPCHK(pooled.take((n_chk + n_part + 2 * nprobes) * sizeof(double), &d_ws));
     for (int j = 0; j < nprobes; ++j) HIPCHK(pooled.take((size_t)std::max<int64_t>(n, 1) * sizeof(double), &pr.p[j]));
     // page-locked staging for the overlaps of every step (a slot of 2*nprobes sums per step), shared with tridiag_run
-    const int64_t want = (int64_t)2 * nprobes * nlanc;
-    if (want > h->probe_ov_n) {
-      if (h->h_probe_ov) (void)hipHostFree(h->h_probe_ov);
-      h->h_probe_ov = nullptr;
-      h->probe_ov_n = 0;
-      HIPCHK(hipHostMalloc((void**)&h->h_probe_ov, (size_t)want * sizeof(double), hipHostMallocDefault));
-      h->probe_ov_n = want;
-    }
-    return HXV_OK;
+    return ensure_probe_stage(h, (int64_t)2 * nprobes * nlanc);
   };
   int rc = comm_agree(h, prepare());
   if (rc) return rc;
