@@ -2,7 +2,7 @@
 // Ht = (H - b)/a.  The product H t_n is the engine's own (apply_slab, no epilogue); what is here is everything else a step does, in ONE pass
 // over the vectors: the linear combination, the running sum  out += c_{n+1} t_{n+1},  the overlaps of t_{n+1} with up to HXV_MAX_PROBES probe
 // vectors, and the two self-overlaps <t_{n+1}|t_{n+1}>, <t_{n+1}|t_n> that give two diagonal moments per product.
-// COMPLEX VECTORS ONLY (double2 elements, this rank's slab of qdw * pitch elements): a real-vector form is not provided.
+// COMPLEX VECTORS (double2 elements, this rank's slab of qdw * pitch elements); the real-vector form is hxv_chebyshev_real_kernels.hpp.
 // Pad rows are zero in every input; they come out as +0.0 and enter every sum as zeros.
 // Reductions as everywhere in the engine (hxv_lanczos_kernels.hpp): per-thread sums in the order of the grid-stride loop, products rounded
 // before they are added, block_sum's fixed 256-entry LDS tree, one partial per workgroup and accumulator, and lz_probe_final on ONE workgroup

@@ -50,6 +50,10 @@ module ED_HAMILTONIAN_GPU_HXV
   !Chebyshev recurrence: moments and f(H) on a device-resident state (include/hxv.h: hxv_chebyshev_moments, hxv_chebyshev_apply)
   public :: gpu_chebyshev_moments_dev
   public :: gpu_chebyshev_apply_dev
+  !the same on real vectors (real H, real start vector and probes), and the seeded random device state they start from
+  public :: gpu_chebyshev_moments_real_dev
+  public :: gpu_chebyshev_apply_real_dev
+  public :: gpu_vector_random_dev
   public :: gpu_vector_to_host
   public :: gpu_vector_from_host
   public :: gpu_free_vector
@@ -437,6 +441,29 @@ module ED_HAMILTONIAN_GPU_HXV
        real(c_double),value                 :: a,b
        real(c_double)                       :: norm2
      end function hxv_chebyshev_apply
+     integer(c_int) function hxv_chebyshev_moments_real(h,d_vin,nprobes,d_probes,nmom,a,b,moments,self_moments) bind(C,name="hxv_chebyshev_moments_real")
+       import :: c_int, c_int32_t, c_ptr, c_double
+       type(c_ptr),value         :: h,d_vin
+       integer(c_int32_t),value  :: nprobes,nmom
+       type(c_ptr)               :: d_probes(*)
+       real(c_double),value      :: a,b
+       real(c_double)            :: moments(*)
+       real(c_double)            :: self_moments(*)
+     end function hxv_chebyshev_moments_real
+     integer(c_int) function hxv_chebyshev_apply_real(h,d_vin,ncoef,coef,a,b,d_out,norm2) bind(C,name="hxv_chebyshev_apply_real")
+       import :: c_int, c_int32_t, c_ptr, c_double
+       type(c_ptr),value         :: h,d_vin,d_out
+       integer(c_int32_t),value  :: ncoef
+       real(c_double),intent(in) :: coef(*)
+       real(c_double),value      :: a,b
+       real(c_double)            :: norm2
+     end function hxv_chebyshev_apply_real
+     integer(c_int) function hxv_vector_random(h,seed,complex_valued,d_vec) bind(C,name="hxv_vector_random")
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr),value        :: h,d_vec
+       integer(c_int64_t),value :: seed            !(uint64_t: the same 64 bits)
+       integer(c_int32_t),value :: complex_valued
+     end function hxv_vector_random
   end interface
 
   type(c_ptr),save :: handle = c_null_ptr   !one open sector at a time (ED_HAMILTONIAN_COMMON.f90:17-18)
@@ -1005,6 +1032,79 @@ contains
     call check(hxv_chebyshev_apply(handle,vin%d,int(size(coef),c_int32_t),cf,a,b,out%d,n2),"gpu_chebyshev_apply_dev")
     if(present(norm2))norm2=n2
   end subroutine gpu_chebyshev_apply_dev
+
+  !> gpu_chebyshev_moments_dev on REAL vectors (include/hxv.h, hxv_chebyshev_moments_real): a real H, vin and the probes purely real (device
+  !! vectors of the open sector in their ordinary layout); moments are REAL.  Half the bytes per order.  An imaginary part in a vector, or a
+  !! sector without real vectors, stops the program with the engine's message.
+  subroutine gpu_chebyshev_moments_real_dev(vin,probes,a,b,moments,self_moments)
+    type(gpu_vector),intent(in)      :: vin
+    type(gpu_vector),intent(in)      :: probes(:)
+    real(8),intent(in)               :: a,b
+    real(8),intent(inout)            :: moments(:,:)
+    real(8),intent(inout),optional   :: self_moments(:)
+    type(c_ptr)                      :: plist(8)
+    real(8),allocatable              :: mom(:,:),smom(:)
+    integer                          :: j,nmom
+    if(.not.c_associated(handle))stop "gpu_chebyshev_moments_real_dev ERROR: Hsector NOT set"
+    if(vin%sector_id/=handle_serial.or..not.c_associated(vin%d))stop "gpu_chebyshev_moments_real_dev ERROR: the start vector does not belong to the open sector"
+    if(size(probes)>8)stop "gpu_chebyshev_moments_real_dev ERROR: more than 8 probes"
+    nmom=size(moments,2)
+    if(size(moments,1)/=size(probes).or.nmom<1)stop "gpu_chebyshev_moments_real_dev ERROR: moments must be (size(probes),nmom), nmom >= 1"
+    if(present(self_moments))then
+       if(size(self_moments)/=2*nmom-1)stop "gpu_chebyshev_moments_real_dev ERROR: self_moments must have 2*nmom-1 entries"
+    endif
+    plist=c_null_ptr
+    do j=1,size(probes)
+       if(probes(j)%sector_id/=handle_serial.or..not.c_associated(probes(j)%d))stop "gpu_chebyshev_moments_real_dev ERROR: a probe does not belong to the open sector"
+       plist(j)=probes(j)%d
+    enddo
+    allocate(mom(max(size(probes),1),nmom),smom(2*nmom-1))      !(contiguous, whatever section the caller passed)
+    call check(hxv_chebyshev_moments_real(handle,vin%d,int(size(probes),c_int32_t),plist,int(nmom,c_int32_t),a,b,mom,smom),"gpu_chebyshev_moments_real_dev")
+    if(size(probes)>0)moments=mom
+    if(present(self_moments))self_moments=smom
+  end subroutine gpu_chebyshev_moments_real_dev
+
+  !> gpu_chebyshev_apply_dev on REAL vectors (include/hxv.h, hxv_chebyshev_apply_real): a real H, a purely real vin, REAL coefficients.
+  !! out has an imaginary part of exactly zero and is written only when the call succeeds.
+  subroutine gpu_chebyshev_apply_real_dev(vin,coef,a,b,out,norm2)
+    type(gpu_vector),intent(in)    :: vin
+    real(8),intent(in)             :: coef(:)
+    real(8),intent(in)             :: a,b
+    type(gpu_vector),intent(inout) :: out
+    real(8),intent(out),optional   :: norm2
+    real(8),allocatable            :: cf(:)
+    real(8)                        :: n2
+    if(.not.c_associated(handle))stop "gpu_chebyshev_apply_real_dev ERROR: Hsector NOT set"
+    if(vin%sector_id/=handle_serial.or..not.c_associated(vin%d))stop "gpu_chebyshev_apply_real_dev ERROR: the start vector does not belong to the open sector"
+    if(size(coef)<1)stop "gpu_chebyshev_apply_real_dev ERROR: at least one coefficient"
+    if(.not.c_associated(out%d))then
+       call check(hxv_vector_alloc(handle,out%d),"gpu_chebyshev_apply_real_dev")
+       call vec_born(out,out%d,.false.)
+    endif
+    if(out%sector_id/=handle_serial)stop "gpu_chebyshev_apply_real_dev ERROR: the output does not belong to the open sector"
+    allocate(cf(size(coef))); cf=coef                           !(contiguous, whatever section the caller passed)
+    n2=0d0
+    call check(hxv_chebyshev_apply_real(handle,vin%d,int(size(coef),c_int32_t),cf,a,b,out%d,n2),"gpu_chebyshev_apply_real_dev")
+    if(present(norm2))norm2=n2
+  end subroutine gpu_chebyshev_apply_real_dev
+
+  !> A seeded random device vector of the open sector (include/hxv.h, hxv_vector_random): components uniform in [-0.5,0.5), not
+  !! normalised; real-valued (imaginary part exactly zero) unless complex_valued.  The same seed gives the same vector whatever the device
+  !! row order or the rank split.  An empty vec is allocated on the open sector.
+  subroutine gpu_vector_random_dev(seed,vec,complex_valued)
+    integer(8),intent(in)          :: seed
+    type(gpu_vector),intent(inout) :: vec
+    logical,intent(in),optional    :: complex_valued
+    integer(c_int32_t)             :: cv
+    if(.not.c_associated(handle))stop "gpu_vector_random_dev ERROR: Hsector NOT set"
+    if(.not.c_associated(vec%d))then
+       call check(hxv_vector_alloc(handle,vec%d),"gpu_vector_random_dev")
+       call vec_born(vec,vec%d,.false.)
+    endif
+    if(vec%sector_id/=handle_serial)stop "gpu_vector_random_dev ERROR: the vector does not belong to the open sector"
+    cv=0; if(present(complex_valued))cv=merge(1,0,complex_valued)
+    call check(hxv_vector_random(handle,int(seed,c_int64_t),cv,vec%d),"gpu_vector_random_dev")
+  end subroutine gpu_vector_random_dev
 
   !> TWO gpu_sp_lanc_tridiag_probes_dev runs on one product per step (real H; include/hxv.h, hxv_lanczos_tridiag_pair_probes): the start
   !! vectors and the probes are REAL vectors of the open sector (c / c^dagger applied to a real ground state), the probes are shared by both

@@ -1,5 +1,6 @@
-"""Host side of the Chebyshev recurrence (HxvSector.chebyshev_moments / chebyshev_apply, include/hxv.h): the spectral window, the
-coefficient series of e^{-tau H} and e^{-iHt}, the Jackson kernel and the kernel-polynomial reconstruction of a spectral function.
+"""Host side of the Chebyshev recurrence (HxvSector.chebyshev_moments / chebyshev_apply and their _real forms, include/hxv.h): the spectral
+window, the coefficient series of e^{-tau H} and e^{-iHt}, thermal typical states from a seeded device vector, the Jackson kernel and the
+kernel-polynomial reconstruction of a spectral function.
 
 Conventions.  The window (a, b) maps the spectrum into [-1, 1]:  x = (E - b)/a,  a > 0,  spectrum of H inside [b - a, b + a].  A series
 f(E) = sum_n c_n T_n(x) is what chebyshev_apply takes as `coef`.  numpy only: the Bessel values come from this module's own backward
@@ -99,6 +100,25 @@ def propagator_coefficients(t: float, a: float, b: float, tol: float = 1e-14) ->
     c = 2.0 * y * np.array([1.0, -1j, -1.0, 1j])[np.arange(y.size) % 4]  # (-i)^n, exactly
     c[0] = y[0]
     return _truncate(c, tol) * np.exp(-1j * float(b) * float(t))
+
+
+def thermal_state(sec, beta: float, a: float, b: float, seed: int, real: bool | None = None, tol: float = 1e-14):
+    """A thermal typical state  e^{-beta H/2}|r>  of an open sector, entirely on the device: |r> = sec.random_vector(seed) (real-valued on the
+    real path, complex-valued otherwise), the series exp_coefficients(beta/2, a, b, tol) and one chebyshev_apply[_real].  (a, b): a window
+    around the spectrum (spectral_window).  real = None takes the real-vector path where sec.real_vectors_available; real = True on a sector
+    without real vectors raises; real = False runs on complex vectors.  -> (out, norm2 = <out|out>), out in the padded layout.  Collective
+    on a split sector."""
+    from .engine import HxvError
+
+    if real is None:
+        real = bool(sec.real_vectors_available)
+    elif real and not sec.real_vectors_available:
+        raise HxvError("thermal_state(real=True): real vectors are not available on this sector (complex amplitudes, the spH0nd block or debug options)")
+    r = sec.random_vector(seed, complex_valued=not real)
+    coef = exp_coefficients(0.5 * float(beta), a, b, tol)
+    if real:
+        return sec.chebyshev_apply_real(r, coef.real, a, b)
+    return sec.chebyshev_apply(r, coef, a, b)
 
 
 def jackson(N: int) -> np.ndarray:

@@ -51,7 +51,8 @@ EXPORTS = [
     "hxv_obs_record_elems", "hxv_observables_accumulate", "hxv_obs_derived_elems", "hxv_observables_derive",
     "hxv_cluster_dm_elems", "hxv_cluster_dm_accumulate", "hxv_reduced_dm_elems", "hxv_reduced_dm_accumulate", "hxv_twin_vector", "hxv_twin_split_plan",
     "hxv_lanczos_tridiag_probes", "hxv_gf_from_probes", "hxv_apply_density_ops", "hxv_lanczos_tridiag_pair_probes", "hxv_apply_spin_pair",
-    "hxv_apply_one_body", "hxv_chebyshev_moments", "hxv_chebyshev_apply",
+    "hxv_apply_one_body", "hxv_chebyshev_moments", "hxv_chebyshev_apply", "hxv_chebyshev_moments_real", "hxv_chebyshev_apply_real",
+    "hxv_vector_random",
 ]
 
 _lib = None
@@ -178,6 +179,9 @@ def load_library():
     L.hxv_apply_one_body.argtypes = [vp, i32, pi32, pi32, pi32, pd, i32, vp, vp, pd, pd]
     L.hxv_chebyshev_moments.argtypes = [vp, vp, i32, C.POINTER(vp), i32, dbl, dbl, pd, pd]
     L.hxv_chebyshev_apply.argtypes = [vp, vp, i32, pd, dbl, dbl, vp, pd]
+    L.hxv_chebyshev_moments_real.argtypes = [vp, vp, i32, C.POINTER(vp), i32, dbl, dbl, pd, pd]
+    L.hxv_chebyshev_apply_real.argtypes = [vp, vp, i32, pd, dbl, dbl, vp, pd]
+    L.hxv_vector_random.argtypes = [vp, C.c_uint64, i32, vp]
     _lib = L
     return L
 
@@ -1164,6 +1168,62 @@ class HxvSector:
         _chk(load_library().hxv_chebyshev_apply(self._h, vin.data_ptr(), cf.size, C.cast(cf.ctypes.data, C.POINTER(C.c_double)), a, b,
                                                 out.data_ptr(), C.byref(n2)), "hxv_chebyshev_apply")
         return out, n2.value
+
+    def chebyshev_moments_real(self, vin, probes, nmom: int, a: float, b: float):
+        """hxv_chebyshev_moments_real (include/hxv.h): chebyshev_moments for a real H with purely real vin and probes, on real vectors inside
+        (half the bytes per order).  vin and the probes are device vectors in the ordinary padded complex layout; any imaginary part in
+        one of them, or a sector without real vectors (real_vectors_available), raises HxvError.
+        -> (moments[nmom, nprobes] float64 = <p_j|t_n>, self_moments[2*nmom - 1] float64)."""
+        import torch
+
+        probes = list(probes)
+        for v in [vin] + probes:
+            self._padded(v, "chebyshev_moments_real")
+        torch.cuda.synchronize(vin.device)
+        npr = len(probes)
+        mom = np.zeros((max(nmom, 0), npr), dtype=np.float64)
+        smom = np.zeros(max(2 * nmom - 1, 1))
+        plist = (C.c_void_p * max(npr, 1))(*[p.data_ptr() for p in probes])
+        _chk(load_library().hxv_chebyshev_moments_real(self._h, vin.data_ptr(), npr, plist if npr else None, nmom, a, b,
+                                                       _p(mom, C.c_double) if npr else None, _p(smom, C.c_double)),
+             "hxv_chebyshev_moments_real")
+        return mom, smom
+
+    def chebyshev_apply_real(self, vin, coef, a: float, b: float, out=None):
+        """hxv_chebyshev_apply_real (include/hxv.h): chebyshev_apply for a real H, a purely real vin and REAL coefficients (a complex `coef`
+        with a non-zero imaginary part is refused), on real vectors inside.  out: a device vector in the padded complex layout, allocated
+        when not given; its imaginary part comes out exactly zero and it is written only on success.  -> (out, norm2 = <out|out>)."""
+        import torch
+
+        self._padded(vin, "chebyshev_apply_real")
+        cf = np.atleast_1d(np.asarray(coef))
+        if np.iscomplexobj(cf):
+            if np.any(cf.imag != 0.0):
+                raise HxvError("chebyshev_apply_real takes real coefficients: coef has a non-zero imaginary part (chebyshev_apply takes complex ones)")
+            cf = cf.real
+        cf = np.ascontiguousarray(cf, dtype=np.float64)
+        if out is None:
+            out = torch.empty(self.localElems, dtype=torch.complex128, device=vin.device)
+        self._padded(out, "chebyshev_apply_real")
+        torch.cuda.synchronize(vin.device)
+        n2 = C.c_double()
+        _chk(load_library().hxv_chebyshev_apply_real(self._h, vin.data_ptr(), cf.size, _p(cf, C.c_double), a, b, out.data_ptr(), C.byref(n2)),
+             "hxv_chebyshev_apply_real")
+        return out, n2.value
+
+    def random_vector(self, seed: int, complex_valued: bool = False, out=None):
+        """hxv_vector_random (include/hxv.h): a seeded random device vector of this sector (this rank's slab; local, not collective) in the
+        padded layout, components uniform in [-0.5, 0.5), not normalised; real (imaginary part exactly zero) unless complex_valued.  The
+        same (seed, sector) gives the same vector in the reference's layout whatever the device row order, the rank split or the handle
+        kind.  out: a device vector to fill, allocated when not given."""
+        import torch
+
+        if out is None:
+            out = torch.empty(self.localElems, dtype=torch.complex128, device=self._dev())
+        self._padded(out, "random_vector")
+        torch.cuda.synchronize(out.device)
+        _chk(load_library().hxv_vector_random(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(complex_valued)), out.data_ptr()), "hxv_vector_random")
+        return out
 
     def time_lanczos(self, nrep: int) -> float:
         import torch

@@ -400,8 +400,9 @@ int hxv_gf_from_probes(int32_t nsteps, const double *alanc, const double *blanc,
  * of the kernel polynomial method.  Per order: ONE product (the engine's own, through the slab product without an epilogue) and ONE fused
  * streaming pass that forms t_{n+1} over t_{n-1}, adds c_{n+1} t_{n+1} to the running sum, and reduces the overlaps with the probes together
  * with <t_{n+1}|t_{n+1}> and <t_{n+1}|t_n>; (3 + M)*16 bytes per state for M probes, (4 + M)*16 with a running sum.  No floating-point
- * atomics: the same vectors on the same handle give the same bits on every call.  COMPLEX VECTORS ONLY: a real-vector form is not provided,
- * option "real_vectors" does not apply.
+ * atomics: the same vectors on the same handle give the same bits on every call.  These two entries run on COMPLEX vectors whatever H is,
+ * and option "real_vectors" does not apply to them; for a real H with real vectors the REAL-vector forms below do the same work at half
+ * the bytes.  The choice is the caller's, by the entry's name: nothing selects the real path automatically.
  * hxv_chebyshev_moments:
  *   moments[2*(n*nprobes + j)], [.. + 1] = Re, Im <p_j|T_n(Ht)|v> = sum conj(p_j[i]) t_n[i]  for n < nmom, from nmom - 1 products.  d_probes as
  *     in hxv_lanczos_tridiag_probes (used as given; a probe may be d_vin itself); nprobes = 0: d_probes and moments may be NULL.
@@ -431,6 +432,40 @@ int hxv_chebyshev_moments(hxv_handle *h, const void *d_vin, int32_t nprobes, con
                           double *self_moments /* [2*nmom-1] real, may be NULL */);
 int hxv_chebyshev_apply(hxv_handle *h, const void *d_vin, int32_t ncoef, const double *coef /* [ncoef] complex */, double a, double b,
                         void *d_out, double *norm2 /* <out|out>, may be NULL */);
+/* REAL-VECTOR FORMS of the two entries above, for a real H (every cdn_hm_* model) and purely real d_vin and probes: thermal typical states
+ * e^{-beta H/2}|r> and the moments of a real start vector never leave the reals.  The vectors AT THE BOUNDARY stay in the handle's ordinary
+ * complex padded layout, as with the Lanczos drivers; inside, the recurrence runs on real blocks double[qdw][pitch_real] from the buffer
+ * cache: d_vin and the probes are converted once at the start, d_out is converted back once at the end.  Per order: the real product
+ * (apply_slab_real, no epilogue), one real streaming pass -- (3 + M)*8 bytes per state, (4 + M)*8 with a running sum -- ONE all-reduce of
+ * nprobes + 2 sums and ONE stream synchronisation.  Windows, guard, self-moment formulas, split sectors (the exchange moves real slabs),
+ * refusals of vectors in a gather buffer and the agreement before the first collective are those of the complex entries.
+ *   moments[n*nprobes + j] = <p_j|T_n(Ht)|v>, REAL;  self_moments as above;  coef[n] REAL.
+ *   d_out: the imaginary part of every element is exactly +0.0.  d_out is written ONLY ON SUCCESS: after any error return it holds what it
+ *     held before the call (the running sum lives in a cache block until the last order is done).
+ *   SCRATCH: 3 + nprobes (+ 1 with d_out) real vector-sized blocks and one small one, back in the cache on every way out.
+ * Option "real_vectors" does NOT gate these entries: the caller asked for the real form by name.
+ * Errors: HXV_ERR_UNSUPPORTED, with the blocker's text, where hxv_real_vectors_available(h) is 0 (complex amplitudes, the spH0nd block, the
+ * tiled kernels not in use, debug options); HXV_ERR_ARG when d_vin or any probe has a non-zero (or non-finite) imaginary part -- the sum of
+ * |Im| over all of them and all ranks in one reduction, so every rank of a split sector decides alike -- and for everything the complex
+ * entries refuse. */
+int hxv_chebyshev_moments_real(hxv_handle *h, const void *d_vin, int32_t nprobes, const void *const *d_probes, int32_t nmom, double a,
+                               double b, double *moments /* [nmom][nprobes] REAL, order-major; NULL iff nprobes == 0 */,
+                               double *self_moments /* [2*nmom-1] real, may be NULL */);
+int hxv_chebyshev_apply_real(hxv_handle *h, const void *d_vin, int32_t ncoef, const double *coef /* [ncoef] REAL */, double a, double b,
+                             void *d_out, double *norm2 /* <out|out>, may be NULL */);
+/* A SEEDED RANDOM STATE on the device: the start vector of the typical-state methods, without numpy over Dim elements and a host-to-device
+ * copy.  Local, not collective; any handle (hxv_create_from_csr included), no basis maps needed.  ONE streaming kernel writes every element
+ * of d_vec (hxv_localvec_elems() elements, padded layout), pad rows zero, and the call returns when it is done.
+ * The value of an element depends only on (seed, I, c), I = col * DimUp + reference row the GLOBAL index in the reference's order, c the
+ * component, so a sector gets the same vector whatever its device row order, rank split or handle kind (hxv_vector_to_host gives the same
+ * host array).  With mix(x) the splitmix64 finaliser  x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ * x = (x ^ (x >> 27)) * 0x94D049BB133111EB;  x ^ (x >> 31)  (64-bit wrap-around arithmetic):
+ *     key = mix(seed),     u(I, c) = (double)(mix(key ^ (2*I + c)) >> 11) * 2^-53 - 0.5          uniform in [-0.5, 0.5)
+ *     complex_valued = 0:  element I = (u(I, 0), +0.0 exactly);      complex_valued = 1:  element I = (u(I, 0), u(I, 1)).
+ * Vectors of different seeds are independent samples (the key is hashed before it meets the index: no seed is a shifted copy of another);
+ * not normalised: <v|v> ~ Dim/12 per component.
+ * Errors: HXV_ERR_ARG for a NULL handle or vector, complex_valued outside {0, 1}. */
+int hxv_vector_random(hxv_handle *h, uint64_t seed, int32_t complex_valued, void *d_vec);
 /* ---- Several lowest eigenpairs on device: the call SciFortran's sp_eigh (P-ARPACK) serves at ED_DIAG.f90:152-160,
  *   call sp_eigh(spHtimesV_p, eig_values(Neigen), eig_basis(vecDim,Neigen), Nblock, Nitermax, tol=lanc_tolerance)
  * as a thick-restart Lanczos (the explicit-restart form of ARPACK's implicitly restarted Lanczos for Hermitian

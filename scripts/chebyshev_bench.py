@@ -1,5 +1,8 @@
-"""Cost of the Chebyshev recurrence (include/hxv.h: hxv_chebyshev_moments, hxv_chebyshev_apply) per order at C3, sector (8,8), next to the
-product alone and to device-to-device copies.
+"""Cost of the Chebyshev recurrence (include/hxv.h: hxv_chebyshev_moments, hxv_chebyshev_apply and their _real forms) per order at C3, sector
+(8,8), next to the product alone and to device-to-device copies; and of hxv_vector_random next to a copy and to vector_from_host.
+Section "real" of the output: the same measurements on the real-vector path of the same build (real product, real drivers with the complex
+per-order time beside them, the real step kernel through tests/device/chebyshev_real_kernels_check.hip with (3 + M) * 8 B per state, its
+time per byte of its own traffic over the copy's).
 
   python scripts/chebyshev_bench.py [--orders 10] [--reps 5] [--warmup 2] [--out profiles/chebyshev_bench.json]
 
@@ -139,6 +142,70 @@ def main():
             res["step_kernel"][key] = dict(probes=M, running_sum=with_sum, kernel_ms=k_ms, copy_bytes=nb, copy_ms=c_ms, ratio_to_copy=k_ms["median_ms"] / c_ms["median_ms"],
                                            kernel_traffic_bytes=traffic, kernel_GBps=traffic / k_ms["median_ms"] / 1e6, copy_GBps=2 * nb / c_ms["median_ms"] / 1e6)
             print(json.dumps({key: res["step_kernel"][key]}), flush=True)
+
+    # ---- the REAL-vector path of the same build: the product alone, the drivers per order, the step kernel alone, the random vector
+    res["real"] = real = dict(available=bool(sec.real_vectors_available), drivers={}, step_kernel={})
+    if real["available"]:
+        def real_vector(seed):
+            v = vector(seed)
+            v.imag.zero_()
+            return v / torch.linalg.vector_norm(v)
+
+        rpsi = real_vector(1)
+        rprobes = [real_vector(10 + j) for j in range(8)]
+        nr = hxv.load_library().hxv_realvec_elems(sec._h)       # DimDw * pitch_real doubles
+        rv, rhv = torch.zeros(nr, dtype=torch.float64, device="cuda"), torch.zeros(nr, dtype=torch.float64, device="cuda")
+        rv.normal_(generator=torch.Generator(device="cuda").manual_seed(5))
+        pr = nr // sec.DimDw
+        rv.view(sec.DimDw, pr)[:, sec.DimUp:] = 0
+        real["vector_bytes"] = 8 * nr
+        real["product"] = _stats(_event_ms(lambda: sec.apply_device_real(rv, rhv), a.warmup, a.reps * 2))
+        rp_ms = real["product"]["median_ms"]
+        rcoef = np.ones(K + 1) / (K + 1)
+        runs = [(f"moments_{M}_probes", M, (lambda M=M: sec.chebyshev_moments_real(rpsi, rprobes[:M], K + 1, wa, wb)),
+                 (lambda M=M: sec.chebyshev_moments_real(rpsi, rprobes[:M], 1, wa, wb))) for M in (0, 1, 4, 8)]
+        runs.append(("apply", 0, lambda: sec.chebyshev_apply_real(rpsi, rcoef, wa, wb, out=out), lambda: sec.chebyshev_apply_real(rpsi, rcoef[:1], wa, wb, out=out)))
+        for name, M, full, none in runs:
+            t_full, t_none = _stats(_event_ms(full, a.warmup, a.reps)), _stats(_event_ms(none, a.warmup, a.reps))
+            per = (t_full["median_ms"] - t_none["median_ms"]) / K
+            cper = res["drivers"][name]["per_order_ms"]
+            real["drivers"][name] = dict(probes=M, run_ms=t_full, run_without_products_ms=t_none, per_order_ms=per, per_order_minus_product_ms=per - rp_ms,
+                                         per_order_over_product=per / rp_ms, complex_per_order_ms=cper, complex_over_real=cper / per)
+            print(json.dumps({"real " + name: real["drivers"][name]}), flush=True)
+        # the real step kernel on the driver's grid for n2 = nr / 2 double2 elements; the buffers are the front halves of the complex ones
+        LR = C.CDLL(str(ge.build_chebyshev_real_kernels_check()))
+        LR.crk_step.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, C.POINTER(vp), dbl, dbl, dbl, vp, vp]
+        n2 = nr // 2
+        rgrid = L.ckc_grid_for(n2)
+        real["grid"] = rgrid
+        for with_sum in (False, True):
+            for M in (0, 1, 4, 8):
+                def rstep():
+                    rc = LR.crk_step(rgrid, M, 0, n2, hv.data_ptr(), cur.data_ptr(), prev.data_ptr(), out.data_ptr() if with_sum else None, plist if M else None,
+                                     0.5, 0.25, 0.125, part.data_ptr(), sums.data_ptr())
+                    assert rc == 0, rc
+                k_ms = _stats(_clock_ms(rstep, a.warmup, a.reps))
+                nvec = (4 if with_sum else 3) + M
+                nb = 8 * nr * nvec
+                c_ms = _stats(_event_ms(lambda: dst[:nb].copy_(src[:nb]), a.warmup, a.reps))
+                traffic = 8 * nr * (nvec + (2 if with_sum else 1))
+                key = f"M{M}_{'sum' if with_sum else 'nosum'}"
+                kg, cg = traffic / k_ms["median_ms"] / 1e6, 2 * nb / c_ms["median_ms"] / 1e6
+                real["step_kernel"][key] = dict(probes=M, running_sum=with_sum, kernel_ms=k_ms, copy_bytes=nb, copy_ms=c_ms, ratio_to_copy=k_ms["median_ms"] / c_ms["median_ms"],
+                                                kernel_traffic_bytes=traffic, kernel_GBps=kg, copy_GBps=cg, time_per_byte_over_copy=cg / kg,
+                                                complex_kernel_ms=res["step_kernel"][key]["kernel_ms"]["median_ms"])
+                print(json.dumps({"real " + key: real["step_kernel"][key]}), flush=True)
+
+    # ---- the seeded random vector: one streaming pass (16 B written per state) against a device-to-device copy of the vector (16 B read and
+    #      16 B written per state) and against numpy-free vector_from_host of a host array that already exists
+    rnd = torch.empty_like(psi)
+    host = np.zeros(sec.vecDim, dtype=np.complex128)
+    res["random_vector"] = dict(
+        real_ms=_stats(_event_ms(lambda: sec.random_vector(1, False, out=rnd), a.warmup, a.reps)),
+        complex_ms=_stats(_event_ms(lambda: sec.random_vector(1, True, out=rnd), a.warmup, a.reps)),
+        copy_ms=_stats(_event_ms(lambda: rnd.copy_(psi), a.warmup, a.reps)),
+        vector_from_host_ms=_stats(_clock_ms(lambda: sec.vector_from_host(host), 1, max(a.reps // 2, 2))), bytes_written=16 * n)
+    print(json.dumps({"random_vector": res["random_vector"]}), flush=True)
     sec.close()
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     with open(a.out, "w") as f:
