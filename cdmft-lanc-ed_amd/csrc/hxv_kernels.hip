@@ -66,11 +66,11 @@ hipError_t launch_pack_columns(const double2* d_in, double2* d_out, const int32_
 
 hipError_t launch_add_pieces(void* hv, const WtRange* wtr, int nwtr, int dimup, int pitch, int ncols, bool real, hipStream_t st) {
   if (ncols <= 0) return hipSuccess;
-  const dim3 grid((unsigned)std::min((dimup + 255) / 256, 64), (unsigned)ncols);
+  const dim3 grid((unsigned)std::min((dimup + 255) / 256, 64), (unsigned)std::min(ncols, 65535));   // (the kernel loops over the columns past the grid)
   if (real)
-    hipLaunchKernelGGL(add_pieces_kernel<double>, grid, dim3(256), 0, st, (double*)hv, wtr, nwtr, dimup, pitch);
+    hipLaunchKernelGGL(add_pieces_kernel<double>, grid, dim3(256), 0, st, (double*)hv, wtr, nwtr, dimup, pitch, ncols);
   else
-    hipLaunchKernelGGL(add_pieces_kernel<double2>, grid, dim3(256), 0, st, (double2*)hv, wtr, nwtr, dimup, pitch);
+    hipLaunchKernelGGL(add_pieces_kernel<double2>, grid, dim3(256), 0, st, (double2*)hv, wtr, nwtr, dimup, pitch, ncols);
   return hipGetLastError();
 }
 

@@ -20,16 +20,18 @@ __global__ void __launch_bounds__(256) pack_columns_kernel(const double2* __rest
 
 // hv += the dw part, read where the second transpose of exchange mode 2 left it (one block per rank of origin, WtRange): the last step of
 // the OVERLAPPED form of that exchange, where diagonal + up hops ran on a second stream while the transposes were under way.
+// The blocks along y loop over the ncols local columns: a grid holds at most 65535 blocks along y, a skinny sector keeps more columns.
 template <typename VT>
-__global__ void __launch_bounds__(256) add_pieces_kernel(VT* __restrict__ hv, const WtRange* __restrict__ wtr, int nwtr, int dimup, int pitch) {
-  const int c = blockIdx.y;
+__global__ void __launch_bounds__(256) add_pieces_kernel(VT* __restrict__ hv, const WtRange* __restrict__ wtr, int nwtr, int dimup, int pitch, int ncols) {
   for (int row = blockIdx.x * 256 + threadIdx.x; row < dimup; row += gridDim.x * 256) {
     int k = 0;
     while (k + 1 < nwtr && row >= wtr[k].row1) ++k;
-    const VT* __restrict__ src = reinterpret_cast<const VT*>(wtr[k].base) + (int64_t)c * wtr[k].stride + (row - wtr[k].row0);
-    VT a = hv[(int64_t)c * pitch + row];
-    vadd(a, *src);
-    hv[(int64_t)c * pitch + row] = a;
+    for (int c = blockIdx.y; c < ncols; c += gridDim.y) {
+      const VT* __restrict__ src = reinterpret_cast<const VT*>(wtr[k].base) + (int64_t)c * wtr[k].stride + (row - wtr[k].row0);
+      VT a = hv[(int64_t)c * pitch + row];
+      vadd(a, *src);
+      hv[(int64_t)c * pitch + row] = a;
+    }
   }
 }
 

@@ -493,6 +493,9 @@ std::string build_sector_from_model(const hxv_model& m, int nup, int ndw, int ra
   s.dimdw = (int)s.map_dw.size();
   s.dim = (int64_t)s.dimup * s.dimdw;
   if (nranks > s.dimdw) return "nranks > DimDw: shrink the communicator first (ED_HAMILTONIAN.f90:63-89)";
+  // build_ell's limit, asked here, before seconds of matrix building for a sector it will refuse (a row panel's up dimension is its row
+  // count: build_ell decides that one)
+  if (s.dimdw > (1 << ELL_SRC_BITS) || (panel_rows == 0 && s.dimup > (1 << ELL_SRC_BITS))) return "spin-sector dimension exceeds 2^20 (ELL source index)";
   s.rank = rank; s.nranks = nranks;
   dw_split(s.dimdw, rank, nranks, s.qdw, s.dw0);
   s.ishift = (int64_t)s.dw0 * s.dimup;

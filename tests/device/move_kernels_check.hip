@@ -8,7 +8,7 @@
 // kernel's own block size, waits, and returns the HIP status.  Before launching, every entry refuses (hipErrorInvalidValue) what could make
 // the kernel reach outside what it was given whatever the tables hold: a dimension below 1, a pitch or stride below its dimension or not a
 // multiple of 8, an empty or oversized grid, a NULL the kernel would dereference.  Where blockIdx itself is an index without a guard
-// (pack_columns_kernel's x, add_pieces_kernel's y) the grid IS the column count.  Table CONTENTS are not checked here:
+// (pack_columns_kernel's x) the grid IS the column count.  Table CONTENTS are not checked here:
 // tests/test_move_kernels_ref_cpu.py does that for every case the GPU file runs.
 #include "hxv_ladder_kernels.hpp"
 #include "hxv_move_kernels.hpp"
@@ -92,11 +92,11 @@ int mkc_pack_columns(int ncols, const void* in, void* out, const int32_t* cols, 
   return finish();
 }
 
-// row0, row1, stride, base: HOST arrays of nwtr entries (base: device pointers), made into the WtRange table here; gridDim.y is ncols
-// (blockIdx.y indexes the columns without a guard).  real: add_pieces_kernel<double>, otherwise <double2>.
-int mkc_add_pieces(int gx, int ncols, int real, void* hv, int nwtr, const int32_t* row0, const int32_t* row1, const int64_t* stride,
+// row0, row1, stride, base: HOST arrays of nwtr entries (base: device pointers), made into the WtRange table here; the gy blocks along y
+// loop over the ncols columns (ncols may exceed what a grid holds along y).  real: add_pieces_kernel<double>, otherwise <double2>.
+int mkc_add_pieces(int gx, int gy, int ncols, int real, void* hv, int nwtr, const int32_t* row0, const int32_t* row1, const int64_t* stride,
                    const void* const* base, int dimup, int pitch) {
-  if (bad_grid(gx) || bad_grid(ncols) || nwtr < 1 || bad_pitch(pitch, dimup) || !hv || !row0 || !row1 || !stride || !base) return BAD;
+  if (bad_grid(gx) || bad_grid(gy) || ncols < 1 || nwtr < 1 || bad_pitch(pitch, dimup) || !hv || !row0 || !row1 || !stride || !base) return BAD;
   std::vector<hxv::WtRange> tab(nwtr);
   for (int k = 0; k < nwtr; ++k) {
     if (!base[k] || stride[k] < 0) return BAD;
@@ -110,11 +110,11 @@ int mkc_add_pieces(int gx, int ncols, int real, void* hv, int nwtr, const int32_
     (void)hipFree(d_tab);
     return (int)e;
   }
-  const dim3 grid(gx, ncols);
+  const dim3 grid(gx, gy);
   if (real)
-    hipLaunchKernelGGL(hxv::add_pieces_kernel<double>, grid, dim3(256), 0, nullptr, (double*)hv, d_tab, nwtr, dimup, pitch);
+    hipLaunchKernelGGL(hxv::add_pieces_kernel<double>, grid, dim3(256), 0, nullptr, (double*)hv, d_tab, nwtr, dimup, pitch, ncols);
   else
-    hipLaunchKernelGGL(hxv::add_pieces_kernel<double2>, grid, dim3(256), 0, nullptr, (double2*)hv, d_tab, nwtr, dimup, pitch);
+    hipLaunchKernelGGL(hxv::add_pieces_kernel<double2>, grid, dim3(256), 0, nullptr, (double2*)hv, d_tab, nwtr, dimup, pitch, ncols);
   const int rc = finish();
   (void)hipFree(d_tab);
   return rc;

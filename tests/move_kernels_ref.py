@@ -611,6 +611,10 @@ class AddPieces:
     row1: np.ndarray
     stride: np.ndarray
     gx: int
+    gy: int = field(default=0)          # blocks along y; they loop over the columns.  0: one per column
+
+    def __post_init__(self):
+        self.gy = self.gy or self.ncols
 
     @property
     def nwtr(self):
@@ -640,6 +644,14 @@ def add_pieces_cases():
                 out.append(AddPieces(f"{dimup}-nwtr{nwtr}-{'real' if real else 'complex'}-gx{gx}", real, dimup, roundup8(dimup) + (8 if n % 3 == 0 else 0), 3,
                                      row0, row1, stride, gx))
                 n += 1
+    # fewer blocks along y than columns: the column loop's second and third trips, ragged
+    for real in (False, True):
+        for ncols, gy in ((5, 2), (7, 1)):
+            out.append(AddPieces(f"257-nwtr2-{'real' if real else 'complex'}-cols{ncols}-gy{gy}", real, 257, 264, ncols, np.array([0, 100], dtype=np.int32),
+                                 np.array([100, 257], dtype=np.int32), np.array([101, 160], dtype=np.int64), 2, gy))
+    # more one-row columns than a grid holds along y (65535): what a rank of a skinny sector keeps (DimUp small, DimDw above 2 * 65535)
+    out.append(AddPieces("1-nwtr1-complex-cols70001-gy65535", False, 1, 8, 70001, np.array([0], dtype=np.int32), np.array([1], dtype=np.int32),
+                         np.array([2], dtype=np.int64), 1, 65535))
     return out
 
 
@@ -667,6 +679,7 @@ def add_pieces_ref(c, hv0, pieces, bug=None):
     """hv[col*pitch + row] += piece_k[col*stride_k + row - row0_k] for every row < dimup, k the range with row0_k <= row < row1_k; one IEEE
     add per component; pad rows are not touched"""
     hv = hv0.copy()
+    ncols = min(c.ncols, c.gy) if bug == "add_pieces_no_column_loop" else c.ncols     # (the mistake: one column per block of the grid, no loop)
     for row in range(c.dimup):
         if bug == "add_pieces_range_gt":
             k = 0
@@ -677,7 +690,7 @@ def add_pieces_ref(c, hv0, pieces, bug=None):
             assert len(k) == 1, "the ranges do not tile the rows"
             k = k[0]
         st = int(c.stride[0 if bug == "add_pieces_stride0_for_all" else k])
-        col = np.arange(c.ncols)
+        col = np.arange(ncols)
         dst = col * c.pitch + row
         put(hv[:-1], dst, take(hv0[:-1], dst, "hv") + take(pieces[k][:-1], col * st + row - int(c.row0[k]), "piece"), "hv")
     return hv
@@ -686,6 +699,7 @@ def add_pieces_ref(c, hv0, pieces, bug=None):
 def add_pieces_trips(c):
     t = stride_trips(c.dimup, c.gx)
     t["empty_in_the_middle"] = any(c.row0[k] == c.row1[k] for k in range(1, c.nwtr - 1))
+    t["col_trips"], t["col_ragged"] = -(-c.ncols // c.gy), c.ncols % c.gy != 0
     return t
 
 
@@ -765,7 +779,7 @@ MISTAKES = {
     "ladder_parity_counts_orbital": "ladder", "ladder_create_inverted": "ladder", "ladder_accumulate_ignored": "ladder",
     "ladder_coef_conjugated": "ladder", "ladder_roles_swapped": "ladder",
     "ladder_cols_pad_written": "ladder_cols", "ladder_cols_unreached_unwritten": "ladder_cols", "ladder_cols_recv_off_by_one": "ladder_cols",
-    "add_pieces_range_gt": "add_pieces", "add_pieces_stride0_for_all": "add_pieces",
+    "add_pieces_range_gt": "add_pieces", "add_pieces_stride0_for_all": "add_pieces", "add_pieces_no_column_loop": "add_pieces",
     "rows_sign_by_reference_row": "rows",
 }
 # "parity taken of the target instead of the source" is no mistake: the two states differ in the operator's own orbital only, and par_below

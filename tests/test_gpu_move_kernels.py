@@ -40,7 +40,7 @@ def mkc(built):
     L.mkc_ladder.argtypes = [i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, f64, f64, i32, vp, vp, vp]
     L.mkc_ladder_cols.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, f64, f64, i32]
     L.mkc_pack_columns.argtypes = [i32, vp, vp, vp, i32]
-    L.mkc_add_pieces.argtypes = [i32, i32, i32, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(vp), i32, i32]
+    L.mkc_add_pieces.argtypes = [i32, i32, i32, i32, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(vp), i32, i32]
     L.mkc_rows_ref_to_dev.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32]
     L.mkc_rows_dev_to_ref.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32]
     assert L.mkc_tw() == R.TW and L.mkc_tw_threads() == R.TW_THREADS
@@ -256,7 +256,7 @@ def test_add_pieces(mkc, c):
     hv, d_pieces = dev(hv0), [dev(p) for p in pieces]
     row0, row1 = (C.c_int32 * c.nwtr)(*map(int, c.row0)), (C.c_int32 * c.nwtr)(*map(int, c.row1))
     stride, base = (C.c_int64 * c.nwtr)(*map(int, c.stride)), (C.c_void_p * c.nwtr)(*[p.data_ptr() for p in d_pieces])
-    assert mkc.mkc_add_pieces(c.gx, c.ncols, int(c.real), ptr(hv), c.nwtr, row0, row1, stride, base, c.dimup, c.pitch) == 0
+    assert mkc.mkc_add_pieces(c.gx, c.gy, c.ncols, int(c.real), ptr(hv), c.nwtr, row0, row1, stride, base, c.dimup, c.pitch) == 0
     same(host(hv), R.add_pieces_ref(c, hv0, pieces), c.name)
 
 
@@ -305,7 +305,9 @@ def test_the_launchers_refuse_bad_arguments(mkc):
     r0, r1, s1, b1 = (C.c_int32 * 1)(0), (C.c_int32 * 1)(8), (C.c_int64 * 1)(8), (C.c_void_p * 1)(p)
     nul = (C.c_void_p * 1)(None)
     for gx, nc, nw, du, pt, bb in ((0, 1, 1, 8, 8, b1), (1, 0, 1, 8, 8, b1), (1, 1, 0, 8, 8, b1), (1, 1, 1, 9, 8, b1), (1, 1, 1, 8, 12, b1), (1, 1, 1, 8, 8, nul)):
-        assert L.mkc_add_pieces(gx, nc, 0, p, nw, r0, r1, s1, bb, du, pt) == BAD
+        assert L.mkc_add_pieces(gx, max(nc, 1), nc, 0, p, nw, r0, r1, s1, bb, du, pt) == BAD
+    for gy in (0, 65536):       # (the blocks along y loop over the columns: their number is a grid extent of its own)
+        assert L.mkc_add_pieces(1, gy, 1, 0, p, 1, r0, r1, s1, b1, 8, 8) == BAD
     for fn in (L.mkc_rows_ref_to_dev, L.mkc_rows_dev_to_ref):
         for gx, du, pt, nc, tb in ((0, 8, 8, 1, q), (1, 0, 8, 1, q), (1, 9, 8, 1, q), (1, 8, 12, 1, q), (1, 8, 8, 0, q), (1, 8, 8, 1, None)):
             assert fn(gx, p, p, tb, tb, du, pt, nc) == BAD

@@ -211,6 +211,116 @@ def test_every_plan_option_value(checker, tmp_path_factory, name):
     _report(name, out, sec)
 
 
+# ---- 2b. sectors with a one-spin dimension above 65535 (tests/wide_sectors.py; the GPU runs them in tests/test_gpu_wide_sectors.py) -----
+def _wide_shapes():
+    """name -> dict(sector = a name of wide_sectors.SECTORS or (model key, nup, ndw), shard, exchange, sets, and what the default-option plan
+    must look like: at least `blocks` (up, dw) blocks, at least `outer` (up, dw) out-of-block partners, the row order on or off).  The P
+    sectors take the option sets the GPU file runs on them; the plan checker has no sanitizer run of these shapes."""
+    p_opts = [{o: v} for o, vals in (("cols_per_tile", (2, 8)), ("rows_per_tile", (2, 8)), ("block_order", (0, 1, 2)), ("job_up", (1,))) for v in vals]
+    bits6 = [{"tile_bits_up": 6, "tile_bits_dw": 6}]
+    shapes = {
+        "ns20_10_1": dict(sector="ns20_10_1", sets=[{}] + bits6 + p_opts, blocks=(256, 1), outer=(14, 0), row_order=1),
+        "ns20_1_10": dict(sector="ns20_1_10", sets=[{}] + bits6 + p_opts, blocks=(1, 512), outer=(0, 16), row_order=0),
+        "ns22_11_0": dict(sector=("chain22", 11, 0), sets=[{}], blocks=(1024, 1), outer=(15, 0), row_order=1),
+        "ns22_0_11": dict(sector=("chain22", 0, 11), sets=[{}], blocks=(1, 1024), outer=(0, 15), row_order=0),
+        "ns22_2_1": dict(sector="ns22_2_1", sets=[{}], blocks=(1, 1), outer=(0, 0), row_order=0),
+        "ns24_6_1": dict(sector="ns24_6_1", sets=[{}] + p_opts, blocks=(2510, 1), outer=(32, 0), row_order=0),
+        "ns24_1_6": dict(sector="ns24_1_6", sets=[{}] + p_opts, blocks=(1, 4096), outer=(0, 34), row_order=0),
+    }
+    for ex in (0, 1, 2):
+        shapes[f"ns20_1_10_rank1of2_x{ex}"] = dict(sector="ns20_1_10", shard=(1, 2), exchange=ex, sets=[{}], blocks=(1, 256), outer=(0, 14), row_order=0)
+    return shapes
+
+
+WIDE_NAMES = ["ns22_2_1", "ns20_10_1", "ns20_1_10", "ns22_11_0", "ns22_0_11", "ns24_6_1", "ns24_1_6", "ns20_1_10_rank1of2_x0", "ns20_1_10_rank1of2_x1",
+              "ns20_1_10_rank1of2_x2"]
+
+
+def _wide_model(spec):
+    import wide_sectors as WS
+
+    if isinstance(spec, str):
+        key, nup, ndw = WS.SECTORS[spec]
+    else:
+        key, nup, ndw = spec
+    return key, WS.model(key), (nup, ndw)
+
+
+@pytest.mark.parametrize("name", WIDE_NAMES)
+def test_wide_sector_plans_and_matrices(checker, tmp_path_factory, tmp_path, name):
+    """The six sectors of Ns = 20 to 24 whose one-spin dimension is 134 596 to 705 432, Ns 22 (0,11) and the small Ns 22 (2,1) (Ns > 20: the
+    sector builder searches the sorted basis instead of a 2^Ns table), default options; 64-row blocks (15 444 of them) and the option sets of
+    the GPU file on the sectors with both passes; (1,10) as rank 1 of 2 in the three exchanges.  Every plan passes the table check, none
+    is refused, and on the unsplit shapes the matrices the check compares with are the oracle's, every stored element met once."""
+    from oracle.oracle import OracleSector
+
+    sh = _wide_shapes()[name]
+    key, m, sector = _wide_model(sh["sector"])
+    path = _model_file(tmp_path_factory, "wide_" + key, m)
+    shard, unsplit = sh.get("shard", (0, 1)), "shard" not in sh
+    d = tmp_path / "dump"
+    d.mkdir()
+    rc, out, err, sec = run_checker(checker, path, sector, shard, sh.get("exchange", 0), dump=d if unsplit else None, sets=sh["sets"])
+    _assert_passed(rc, out, err, len(sh["sets"]), name, may_refuse=False)
+    p = out[0][1]
+    assert p["usable"] == 1 and p["row_order"] == sh["row_order"], (name, p)
+    assert p["nblocks_up"] >= sh["blocks"][0] and p["nblocks_dw"] >= sh["blocks"][1], (name, p)
+    assert p["max_outer_up"] >= sh["outer"][0] and p["max_outer_dw"] >= sh["outer"][1], (name, p)
+    for k, s in enumerate(sh["sets"]):
+        q = out[k][1]
+        if s.get("tile_bits_up") == 6:
+            assert max(q["nblocks_up"], q["nblocks_dw"]) == 15444 and max(q["max_outer_up"], q["max_outer_dw"]) >= 25, (name, q)
+        if s.get("job_up") == 1:       # above 65535 up rows pass A never runs as jobs; 20 or 24 up rows in one block may
+            assert q["job_up_active"] == (0 if math.comb(m.Ns, sector[0]) > 65535 else 1), (name, q)
+    _report(name, out, sec)
+    if not unsplit:
+        return
+    orc = OracleSector(m, *sector, 0, min(64, math.comb(m.Ns, sector[1])))
+    nnz = {}
+    for which in ("up", "dw"):
+        rp, cols, vals = orc.csr(which)
+        nnz[which] = int(rp[-1])
+        assert np.array_equal(np.fromfile(d / f"{which}_rowptr.i64", dtype=np.int64), rp), (name, which)
+        assert np.array_equal(np.fromfile(d / f"{which}_cols.i32", dtype=np.int32) + 1, cols), (name, which)
+        got = np.fromfile(d / f"{which}_vals.c128", dtype=np.complex128)
+        assert got.shape == vals.shape
+        if vals.size:
+            assert np.abs(got - vals).max() <= TOL * np.abs(vals).max(), (name, which)
+    assert np.array_equal(np.fromfile(d / "map_up.u32", dtype=np.uint32).astype(np.int64), np.asarray(orc.map_up(), dtype=np.int64))
+    assert np.array_equal(np.fromfile(d / "map_dw.u32", dtype=np.uint32).astype(np.int64), np.asarray(orc.map_dw(), dtype=np.int64))
+    orc.close()
+    for k in range(len(sh["sets"])):
+        assert (out[k][1]["triplets_up"], out[k][1]["triplets_dw"]) == (nnz["up"], nnz["dw"]), (name, k)
+
+
+def test_only_the_dimup_gate_keeps_the_job_kernel_off_the_star_sector(checker, tmp_path_factory):
+    """wide_sectors.GATE: on the star model with 12 block bits and "job_max_blocks" = 256 every condition of job_up_usable but DimUp < 65536
+    holds.  (6,1), 38 760 up rows: pass A is planned as jobs and the job kernel's packed registers expand to the sector's matrix.  (10,1),
+    184 756 rows: the same block shapes, no jobs."""
+    import wide_sectors as WS
+
+    key, m, sector = _wide_model(WS.GATE_SECTOR)
+    path = _model_file(tmp_path_factory, "wide_" + key, m)
+    for sec, active in (((6, 1), 1), (sector, 0)):
+        rc, out, err, _ = run_checker(checker, path, sec, sets=[dict(WS.GATE_OPTIONS)])
+        _assert_passed(rc, out, err, 1, (key, sec), may_refuse=False)
+        p = out[0][1]
+        assert p["nblocks_up"] <= 256 and p["max_block_up"] <= 960 and p["max_outer_up"] <= 8 and p["k_in_up"] <= 24, (sec, p)
+        assert (p["job_up_active"], p["job_checked"]) == (active, active), (sec, p)
+        assert (math.comb(m.Ns, sec[0]) < 65536) == bool(active)
+
+
+def test_a_spin_dimension_above_2_to_the_20_is_refused(checker, tmp_path):
+    """Ns = 24, sector (12,0): C(24,12) = 2 704 156 states of one spin are more than the 20 bits of an ELL source index.  The sector builder
+    says so before it builds any matrix."""
+    from hxv import models
+
+    path = write_model(tmp_path / "chain24.model", models.hm_1dchain(Nlat=4, Nbath=5))
+    rc, out, err, sec = run_checker(checker, path, (12, 0))
+    print(f"refused after {sec:.1f} s")
+    assert rc == 1 and not out and "spin-sector dimension exceeds 2^20" in err, (rc, out, err[-500:])
+
+
 # ---- 3. seeded random sweep ----------------------------------------------------------------------------------------------------------
 FUZZ_SEED0 = 4000
 

@@ -101,7 +101,7 @@ def test_launch_arguments_obey_the_launchers_rules():
         assert pitch_ok(c.pitch, 1) and ((0 <= c.cols) & (c.cols < c.nsrc)).all() and len(set(c.cols)) < len(c.cols), c.name
         assert list(c.cols) != sorted(c.cols)
     for c in R.add_pieces_cases():
-        assert pitch_ok(c.pitch, c.dimup) and c.ncols >= 1 and c.nwtr >= 1, c.name
+        assert pitch_ok(c.pitch, c.dimup) and c.ncols >= 1 and c.nwtr >= 1 and 1 <= c.gx <= 65535 and 1 <= c.gy <= 65535, c.name
         # the ranges tile [0, dimup) in order; every buffer has room for its stride
         assert c.row0[0] == 0 and c.row1[-1] == c.dimup and (c.row0[1:] == c.row1[:-1]).all() and (c.stride > c.row1 - c.row0).all(), c.name
     for c in R.rows_cases():
@@ -153,9 +153,13 @@ def test_the_cases_reach_what_no_sector_offers():
         ap = [c for c in R.add_pieces_cases() if c.real == real]
         assert three_ragged([R.add_pieces_trips(c) for c in ap])
         assert any(R.add_pieces_trips(c)["empty_in_the_middle"] for c in ap) and {c.nwtr for c in ap} == {1, 2, 4, 8}
+        assert any(R.add_pieces_trips(c)["col_trips"] >= 3 and R.add_pieces_trips(c)["col_ragged"] for c in ap)     # the column loop
         for c in ap:        # a row at every row0 and at every row1 - 1 of the ranges that hold rows
             live = c.row1 > c.row0
             assert ((c.row0[live] >= 0) & (c.row1[live] - 1 < c.dimup)).all()
+    # more columns than a grid holds along y, at the largest y extent: the column loop's second trip is the only way to the columns past it
+    wide = [c for c in R.add_pieces_cases() if c.ncols > 65535]
+    assert wide and all(c.gy == 65535 and c.dimup == 1 and R.add_pieces_trips(c)["col_trips"] == 2 and R.add_pieces_trips(c)["col_ragged"] for c in wide)
     for to_dev in (True, False):
         assert three_ragged([R.rows_trips(c, to_dev) for c in R.rows_cases()])
 
