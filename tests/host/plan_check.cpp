@@ -1,6 +1,6 @@
 // Stand-alone tile-plan checker ("plan checker").  No HIP runtime call, no device.
 //
-//   plan_check MODEL nup ndw rank nranks exchange [--panel ROWS] [--dump DIR [--dump-diag]] [name=value ...] [/ name=value ...] ...
+//   plan_check MODEL nup ndw rank nranks exchange [--panel ROWS] [--dump DIR [--dump-diag]] [--job-reach] [name=value ...] [/ name=value ...] ...
 //
 // MODEL is a file with the fields of hxv_model in the array order of HxvSector._model_struct (tests/test_host_plan_check.py writes it).
 // The sector is built by build_sector_from_model (the halo layout with exchange = 1; the row panel of the all-to-all exchange by
@@ -658,6 +658,10 @@ DevSector host_view(const SectorHost& s) {
   return d;
 }
 
+// --job-reach: one JOBREACH line per usable option set, ahead of its PLAN line: what scripts/job_kernel_reach.py needs to say which paths of
+// hxv_up_job the set reaches (per up block: rows : out-of-block slots : in-block bound of each 64-row group)
+bool g_job_reach = false;
+
 // one option set: plan, expand, compare.  Returns false when the plan refused the options with a documented message.
 bool check_plan(const SectorHost& S, const std::vector<std::pair<std::string, long>>& opts, int set_index) {
   TilePlan plan;
@@ -775,6 +779,17 @@ bool check_plan(const SectorHost& S, const std::vector<std::pair<std::string, lo
         if (fits) REQUIRE(nst * stage + 2 * wtb + tab <= K_LDS_BYTES, "job ring (lz %d, wc %d): %d bytes of LDS", lz, wc, nst * stage + 2 * wtb + tab);
       }
   }
+  if (g_job_reach) {
+    const Spin& u = sp[0];
+    printf("JOBREACH set=%d usable=%d qdw=%d ncoef_up=%d k_in=%d k_in_real=%d max_outer=%d job_groups=%d job_stages=%d wt_cols=%d blocks=", set_index, (int)usable,
+           S.qdw, plan.ncoef_up, plan.up.k_in, plan.up.k_in_real, plan.up.max_outer, plan.opt.job_groups, plan.opt.job_stages, plan.opt.wt_cols);
+    for (int kb = 0; kb < plan.up.nblocks; ++kb) {
+      const int n = (int)u.start[kb + 1] - (int)u.start[kb];
+      printf("%s%d:%d:", kb ? ";" : "", n, (int)(u.rs_ptr[kb + 1] - u.rs_ptr[kb]) + (int)(u.bh_ptr[kb + 1] - u.bh_ptr[kb]));
+      for (int g = 0; g < (n + 63) / 64; ++g) printf("%s%d", g ? "/" : "", (int)(u.gmax[u.gstart[kb] + (uint32_t)g] & 0xFFFFu));
+    }
+    printf("\n");
+  }
   const int job_active =
       (plan.opt.job_up == 1 && plan.opt.sort_mode == 0 && usable && job_up_fits(dev, plan, false, std::max(plan.opt.job_cols, plan.opt.wt_cols))) ? 1 : 0;
   printf("PLAN set=%d opts=%s usable=1 tile_bits_up=%d tile_bits_dw=%d nblocks_up=%d nblocks_dw=%d n_in_up=%" PRId64 " n_out_up=%" PRId64 " n_in_dw=%" PRId64
@@ -792,7 +807,7 @@ bool check_plan(const SectorHost& S, const std::vector<std::pair<std::string, lo
 
 int main(int argc, char** argv) {
   if (argc < 7) {
-    fprintf(stderr, "usage: plan_check MODEL nup ndw rank nranks exchange [--panel ROWS] [--dump DIR [--dump-diag]] [name=value ...] [/ name=value ...]\n");
+    fprintf(stderr, "usage: plan_check MODEL nup ndw rank nranks exchange [--panel ROWS] [--dump DIR [--dump-diag]] [--job-reach] [name=value ...] [/ name=value ...]\n");
     return 1;
   }
   ModelFile mf;
@@ -808,6 +823,7 @@ int main(int argc, char** argv) {
     if (arg == "--panel" && a + 1 < argc) panel = atoi(argv[++a]);
     else if (arg == "--dump" && a + 1 < argc) dump = argv[++a];
     else if (arg == "--dump-diag") with_diag = true;
+    else if (arg == "--job-reach") g_job_reach = true;
     else if (arg == "/") sets.emplace_back();
     else {
       const size_t eq = arg.find('=');
