@@ -49,4 +49,17 @@ class CallScope {
   hipStream_t stream_;
   std::vector<std::pair<void*, bool>> held_;  // (block, from the buffer cache?)
 };
+
+// THE scratch of a driver that takes overlaps with probes (both tridiagonalisation drivers, chebyshev_run), carved from ONE pooled block: the
+// block partials of the check of the vectors' imaginary parts, the block partials of one step's sums, and those sums; with it the handle's
+// page-locked staging for n_stage doubles (a copy of the sums into the caller's pageable array could make the runtime wait per step).
+struct ProbeScratch {
+  double *chk = nullptr, *part = nullptr, *sums = nullptr;
+  int take(hxv_handle* h, CallScope& pooled, size_t n_chk, size_t n_part, size_t n_sums, int64_t n_stage) {
+    HIPCHK(pooled.take((n_chk + n_part + n_sums) * sizeof(double), &chk));
+    part = chk + n_chk;
+    sums = part + n_part;
+    return ensure_probe_stage(h, n_stage);
+  }
+};
 }  // namespace hxv

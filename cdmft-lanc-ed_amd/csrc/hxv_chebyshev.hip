@@ -4,6 +4,8 @@
 // through apply_slab / apply_slab_real (no epilogue: the product kernels are the engine's, untouched) and one fused streaming pass
 // (hxv_chebyshev_kernels.hpp, hxv_chebyshev_real_kernels.hpp), whose 2*nprobes + 3 (real: nprobes + 2) sums go through ONE all-reduce on a
 // split sector and reach the host with ONE stream synchronisation per order, where the window guard reads them.
+// The four entries check their arguments through two helpers (check_moments, check_apply); the probe list's check and the carving of the
+// small scratch block are the Lanczos drivers' (check_probe_list, ProbeScratch).
 // Also here: hxv_vector_random, the seeded random device state the typical-state uses of the recurrence start from.
 #include <cmath>
 #include <cstring>
@@ -35,22 +37,22 @@ int chebyshev_run(hxv_handle* h, const char* who, bool real, int rc_args, const 
   const int np = std::max(nprobes, 0);
   const int g = grid_for(n), nc = real ? ch_sums_real(np) : ch_sums(np);
   const int g_chk = real ? grid_for((int64_t)pitr * h->host.qdw) : 0;  // (workgroups of one conversion = its partial sums of |Im|)
-  double* d_ws = nullptr;
+  ProbeScratch ws;  // (partials of an order's sums, the sums, and the partials of the conversions' |Im|; an order's sums staged in the handle's array)
   double2 *d_hv = nullptr, *d_a = nullptr, *d_b = nullptr, *d_sum = nullptr;
   double* real_probe[HXV_MAX_PROBES] = {};
   auto resources = [&]() -> int {
     if (rc_args) return rc_args;
     if (int rcc = need_comm(h, who)) return rcc;
-    HIPCHK(pooled.take(((size_t)(g + 1) * nc + (size_t)(1 + np) * g_chk) * sizeof(double), &d_ws));
+    if (int rcw = ws.take(h, pooled, (size_t)(1 + np) * g_chk, (size_t)g * nc, (size_t)nc, nc)) return rcw;
     HIPCHK(pooled.take(bytes, &d_hv));
     HIPCHK(pooled.take(bytes, &d_a));
     HIPCHK(pooled.take(bytes, &d_b));
     for (int j = 0; real && j < np; ++j) HIPCHK(pooled.take(bytes, &real_probe[j]));
     if (real && d_out) HIPCHK(pooled.take(bytes, &d_sum));
-    return ensure_probe_stage(h, nc);  // (page-locked staging for an order's sums: the handle's own array)
+    return HXV_OK;
   };
   if (int rca = comm_agree(h, resources())) return rca;  // (a rank with bad arguments or without memory tells its peers before the first all-reduce)
-  double *d_part = d_ws, *d_sums = d_ws + (size_t)g * nc, *d_chk = d_sums + nc, *stage = h->h_probe_ov;
+  double *d_part = ws.part, *d_sums = ws.sums, *d_chk = ws.chk, *stage = h->h_probe_ov;
   if (!real) d_sum = d_out;
   LzProbes pr{};
   for (int j = 0; j < nprobes; ++j) pr.p[j] = real ? (const double2*)real_probe[j] : (const double2*)d_probes[j];
@@ -139,7 +141,36 @@ int chebyshev_run(hxv_handle* h, const char* who, bool real, int rc_args, const 
   return HXV_OK;
 }
 
-bool window_ok(double a, double b) { return std::isfinite(a) && std::isfinite(b) && a > 0.0; }
+// The argument checks of the two moments entries and of the two apply entries (who: the entry's name; real: the REAL-vector form, asked for by
+// name, so option "real_vectors" is not consulted: what makes real vectors impossible on this handle is an HXV_ERR_UNSUPPORTED with the
+// blocker's text).
+int check_window(const std::string& who, double a, double b) {
+  if (std::isfinite(a) && std::isfinite(b) && a > 0.0) return HXV_OK;
+  return fail(HXV_ERR_ARG, who + ": the window needs a > 0 and finite a, b");
+}
+int check_real(const hxv_handle* h, const std::string& who, bool real) {
+  const char* why = real ? real_mode_blocker(h) : nullptr;
+  return why ? fail(HXV_ERR_UNSUPPORTED, who + ": real vectors unavailable: " + why) : HXV_OK;
+}
+int check_moments(const hxv_handle* h, const char* who, bool real, const void* d_vin, int nprobes, const void* const* d_probes, int nmom, double a,
+                  double b, const double* moments) {
+  if (int rc = check_real(h, who, real)) return rc;
+  if (!d_vin || nmom < 1) return fail(HXV_ERR_ARG, std::string(who) + ": bad argument (NULL start vector or nmom < 1)");
+  if (int rc = check_window(who, a, b)) return rc;
+  // (the exchange of a product writes this rank's slab into its place in a gather buffer)
+  return check_probe_list(h, who, nprobes, d_probes, moments != nullptr, "the moments array", "the exchange overwrites that place");
+}
+int check_apply(const hxv_handle* h, const char* who, bool real, const void* d_vin, int ncoef, const double* coef, double a, double b, const void* d_out) {
+  const std::string w = who;
+  if (int rc = check_real(h, w, real)) return rc;
+  if (!d_vin || !d_out || !coef || ncoef < 1) return fail(HXV_ERR_ARG, w + ": bad argument (NULL vector or coefficients, or ncoef < 1)");
+  if (d_out == d_vin) return fail(HXV_ERR_ARG, w + ": d_out must not be d_vin");
+  if (int rc = check_window(w, a, b)) return rc;
+  for (int k = 0; k < (real ? ncoef : 2 * ncoef); ++k)  // (complex coefficients are interleaved)
+    if (!std::isfinite(coef[k])) return fail(HXV_ERR_ARG, w + ": a coefficient is not finite");
+  if (comm_ready(h) && comm_in_gather(h, d_out)) return fail(HXV_ERR_ARG, w + ": d_out lies in a gather buffer of the handle (hxv_slab_home): the exchange overwrites that place");
+  return HXV_OK;
+}
 
 }  // namespace
 
@@ -147,69 +178,33 @@ extern "C" {
 
 int hxv_chebyshev_moments(hxv_handle* h, const void* d_vin, int32_t nprobes, const void* const* d_probes, int32_t nmom, double a, double b,
                           double* moments, double* self_moments) {
-  if (!h) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments: NULL handle");
-  auto check_args = [&]() -> int {
-    if (!d_vin || nmom < 1) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments: bad argument (NULL start vector or nmom < 1)");
-    if (!window_ok(a, b)) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments: the window needs a > 0 and finite a, b");
-    if (nprobes < 0 || nprobes > HXV_MAX_PROBES) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments: nprobes must be 0 .. HXV_MAX_PROBES (8)");
-    if (nprobes > 0 && (!d_probes || !moments)) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments: nprobes > 0 needs the probe list and the moments array");
-    for (int j = 0; j < nprobes; ++j) {
-      if (!d_probes[j]) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments: NULL entry in the probe list");
-      // (the exchange of a product writes this rank's slab into its place in a gather buffer)
-      if (comm_ready(h) && comm_in_gather(h, d_probes[j])) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments: a probe lies in a gather buffer of the handle (hxv_slab_home): the exchange overwrites that place");
-    }
-    return HXV_OK;
-  };
-  return chebyshev_run(h, "hxv_chebyshev_moments", false, check_args(), d_vin, nprobes, d_probes, nmom, a, b, nullptr, nullptr, moments, self_moments, nullptr);
+  const char* who = "hxv_chebyshev_moments";
+  if (!h) return fail(HXV_ERR_ARG, std::string(who) + ": NULL handle");
+  const int rc_args = check_moments(h, who, false, d_vin, nprobes, d_probes, nmom, a, b, moments);
+  return chebyshev_run(h, who, false, rc_args, d_vin, nprobes, d_probes, nmom, a, b, nullptr, nullptr, moments, self_moments, nullptr);
 }
 
 int hxv_chebyshev_apply(hxv_handle* h, const void* d_vin, int32_t ncoef, const double* coef, double a, double b, void* d_out, double* norm2) {
-  if (!h) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply: NULL handle");
-  auto check_args = [&]() -> int {
-    if (!d_vin || !d_out || !coef || ncoef < 1) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply: bad argument (NULL vector or coefficients, or ncoef < 1)");
-    if (d_out == d_vin) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply: d_out must not be d_vin");
-    if (!window_ok(a, b)) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply: the window needs a > 0 and finite a, b");
-    for (int k = 0; k < 2 * ncoef; ++k)
-      if (!std::isfinite(coef[k])) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply: a coefficient is not finite");
-    if (comm_ready(h) && comm_in_gather(h, d_out)) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply: d_out lies in a gather buffer of the handle (hxv_slab_home): the exchange overwrites that place");
-    return HXV_OK;
-  };
-  return chebyshev_run(h, "hxv_chebyshev_apply", false, check_args(), d_vin, 0, nullptr, ncoef, a, b, coef, (double2*)d_out, nullptr, nullptr, norm2);
+  const char* who = "hxv_chebyshev_apply";
+  if (!h) return fail(HXV_ERR_ARG, std::string(who) + ": NULL handle");
+  const int rc_args = check_apply(h, who, false, d_vin, ncoef, coef, a, b, d_out);
+  return chebyshev_run(h, who, false, rc_args, d_vin, 0, nullptr, ncoef, a, b, coef, (double2*)d_out, nullptr, nullptr, norm2);
 }
 
-// REAL-vector forms (include/hxv.h): the same checks, then the one driver with `real`.  Asked for by name, so option "real_vectors" is not
-// consulted; what makes real vectors impossible on this handle is an HXV_ERR_UNSUPPORTED with the blocker's text.
+// REAL-vector forms (include/hxv.h): the same checks, then the one driver with `real`.
 int hxv_chebyshev_moments_real(hxv_handle* h, const void* d_vin, int32_t nprobes, const void* const* d_probes, int32_t nmom, double a, double b,
                                double* moments, double* self_moments) {
-  if (!h) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments_real: NULL handle");
-  auto check_args = [&]() -> int {
-    if (const char* why = real_mode_blocker(h)) return fail(HXV_ERR_UNSUPPORTED, std::string("hxv_chebyshev_moments_real: real vectors unavailable: ") + why);
-    if (!d_vin || nmom < 1) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments_real: bad argument (NULL start vector or nmom < 1)");
-    if (!window_ok(a, b)) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments_real: the window needs a > 0 and finite a, b");
-    if (nprobes < 0 || nprobes > HXV_MAX_PROBES) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments_real: nprobes must be 0 .. HXV_MAX_PROBES (8)");
-    if (nprobes > 0 && (!d_probes || !moments)) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments_real: nprobes > 0 needs the probe list and the moments array");
-    for (int j = 0; j < nprobes; ++j) {
-      if (!d_probes[j]) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments_real: NULL entry in the probe list");
-      if (comm_ready(h) && comm_in_gather(h, d_probes[j])) return fail(HXV_ERR_ARG, "hxv_chebyshev_moments_real: a probe lies in a gather buffer of the handle (hxv_slab_home): the exchange overwrites that place");
-    }
-    return HXV_OK;
-  };
-  return chebyshev_run(h, "hxv_chebyshev_moments_real", true, check_args(), d_vin, nprobes, d_probes, nmom, a, b, nullptr, nullptr, moments, self_moments, nullptr);
+  const char* who = "hxv_chebyshev_moments_real";
+  if (!h) return fail(HXV_ERR_ARG, std::string(who) + ": NULL handle");
+  const int rc_args = check_moments(h, who, true, d_vin, nprobes, d_probes, nmom, a, b, moments);
+  return chebyshev_run(h, who, true, rc_args, d_vin, nprobes, d_probes, nmom, a, b, nullptr, nullptr, moments, self_moments, nullptr);
 }
 
 int hxv_chebyshev_apply_real(hxv_handle* h, const void* d_vin, int32_t ncoef, const double* coef, double a, double b, void* d_out, double* norm2) {
-  if (!h) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply_real: NULL handle");
-  auto check_args = [&]() -> int {
-    if (const char* why = real_mode_blocker(h)) return fail(HXV_ERR_UNSUPPORTED, std::string("hxv_chebyshev_apply_real: real vectors unavailable: ") + why);
-    if (!d_vin || !d_out || !coef || ncoef < 1) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply_real: bad argument (NULL vector or coefficients, or ncoef < 1)");
-    if (d_out == d_vin) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply_real: d_out must not be d_vin");
-    if (!window_ok(a, b)) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply_real: the window needs a > 0 and finite a, b");
-    for (int k = 0; k < ncoef; ++k)
-      if (!std::isfinite(coef[k])) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply_real: a coefficient is not finite");
-    if (comm_ready(h) && comm_in_gather(h, d_out)) return fail(HXV_ERR_ARG, "hxv_chebyshev_apply_real: d_out lies in a gather buffer of the handle (hxv_slab_home): the exchange overwrites that place");
-    return HXV_OK;
-  };
-  return chebyshev_run(h, "hxv_chebyshev_apply_real", true, check_args(), d_vin, 0, nullptr, ncoef, a, b, coef, (double2*)d_out, nullptr, nullptr, norm2);
+  const char* who = "hxv_chebyshev_apply_real";
+  if (!h) return fail(HXV_ERR_ARG, std::string(who) + ": NULL handle");
+  const int rc_args = check_apply(h, who, true, d_vin, ncoef, coef, a, b, d_out);
+  return chebyshev_run(h, who, true, rc_args, d_vin, 0, nullptr, ncoef, a, b, coef, (double2*)d_out, nullptr, nullptr, norm2);
 }
 
 // The seeded random state (include/hxv.h): one streaming kernel over this rank's slab, local, on any handle.

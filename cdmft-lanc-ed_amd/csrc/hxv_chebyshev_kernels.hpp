@@ -11,7 +11,7 @@
 // launch each kernel alone with a grid and sizes the driver never passes; the product includes it from hxv_chebyshev.hip only.
 #pragma once
 
-#include "hxv_lanczos_kernels.hpp"  // block_sum, grid_for, LzProbes, lz_probe_final
+#include "hxv_lanczos_kernels.hpp"  // block_sum, grid_for, LzProbes, lz_probe_final, with_probe_count
 
 namespace {
 
@@ -102,22 +102,7 @@ __global__ void __launch_bounds__(256) ch_step(int64_t n, const double2* __restr
 // step 0 on g workgroups, then the block-ordered sum of the partials on one: d_sums[2m+3].  d_part: g * (2m+3) doubles.
 inline void launch_ch_init(int g, hipStream_t st, int m, int64_t n, const double2* v, double2* out, const LzProbes& pr, double c0r, double c0i,
                            double* d_part, double* d_sums) {
-  switch (m) {
-#define HXV_CH_CASE(M) \
-  case M:              \
-    hipLaunchKernelGGL((ch_init<M>), dim3(g), dim3(256), 0, st, n, v, out, pr, c0r, c0i, d_part); \
-    break;
-    HXV_CH_CASE(0)
-    HXV_CH_CASE(1)
-    HXV_CH_CASE(2)
-    HXV_CH_CASE(3)
-    HXV_CH_CASE(4)
-    HXV_CH_CASE(5)
-    HXV_CH_CASE(6)
-    HXV_CH_CASE(7)
-    HXV_CH_CASE(8)
-#undef HXV_CH_CASE
-  }
+  with_probe_count<0>(m, [&](auto M) { hipLaunchKernelGGL((ch_init<M()>), dim3(g), dim3(256), 0, st, n, v, out, pr, c0r, c0i, d_part); });
   hipLaunchKernelGGL(lz_probe_final, dim3(1), dim3(256), 0, st, d_part, g, ch_sums(m), d_sums);
 }
 
@@ -125,22 +110,9 @@ inline void launch_ch_init(int g, hipStream_t st, int m, int64_t n, const double
 template <bool SUM, bool FIRST>
 void launch_ch_step_form(int g, hipStream_t st, int m, int64_t n, const double2* hv, const double2* cur, double2* prev_next, double2* out,
                          const LzProbes& pr, double ch, double cc, double cr, double ci, double* d_part) {
-  switch (m) {
-#define HXV_CH_CASE(M) \
-  case M:              \
-    hipLaunchKernelGGL((ch_step<M, SUM, FIRST>), dim3(g), dim3(256), 0, st, n, hv, cur, prev_next, out, pr, ch, cc, cr, ci, d_part); \
-    break;
-    HXV_CH_CASE(0)
-    HXV_CH_CASE(1)
-    HXV_CH_CASE(2)
-    HXV_CH_CASE(3)
-    HXV_CH_CASE(4)
-    HXV_CH_CASE(5)
-    HXV_CH_CASE(6)
-    HXV_CH_CASE(7)
-    HXV_CH_CASE(8)
-#undef HXV_CH_CASE
-  }
+  with_probe_count<0>(m, [&](auto M) {
+    hipLaunchKernelGGL((ch_step<M(), SUM, FIRST>), dim3(g), dim3(256), 0, st, n, hv, cur, prev_next, out, pr, ch, cc, cr, ci, d_part);
+  });
 }
 inline void launch_ch_step(int g, hipStream_t st, int m, bool first, int64_t n, const double2* hv, const double2* cur, double2* prev_next,
                            double2* out, const LzProbes& pr, double ch, double cc, double cr, double ci, double* d_part, double* d_sums) {

@@ -92,44 +92,16 @@ __global__ void __launch_bounds__(256) ch_step_real(int64_t n, const double2* __
 // step 0 on g workgroups, then the block-ordered sum of the partials on one: d_sums[m+2].  d_part: g * (m+2) doubles.
 inline void launch_ch_init_real(int g, hipStream_t st, int m, int64_t n, const double2* v, double2* out, const LzProbes& pr, double c0,
                                 double* d_part, double* d_sums) {
-  switch (m) {
-#define HXV_CH_CASE(M) \
-  case M:              \
-    hipLaunchKernelGGL((ch_init_real<M>), dim3(g), dim3(256), 0, st, n, v, out, pr, c0, d_part); \
-    break;
-    HXV_CH_CASE(0)
-    HXV_CH_CASE(1)
-    HXV_CH_CASE(2)
-    HXV_CH_CASE(3)
-    HXV_CH_CASE(4)
-    HXV_CH_CASE(5)
-    HXV_CH_CASE(6)
-    HXV_CH_CASE(7)
-    HXV_CH_CASE(8)
-#undef HXV_CH_CASE
-  }
+  with_probe_count<0>(m, [&](auto M) { hipLaunchKernelGGL((ch_init_real<M()>), dim3(g), dim3(256), 0, st, n, v, out, pr, c0, d_part); });
   hipLaunchKernelGGL(lz_probe_final, dim3(1), dim3(256), 0, st, d_part, g, ch_sums_real(m), d_sums);
 }
 
 template <bool SUM, bool FIRST>
 void launch_ch_step_real_form(int g, hipStream_t st, int m, int64_t n, const double2* hv, const double2* cur, double2* prev_next, double2* out,
                               const LzProbes& pr, double ch, double cc, double cr, double* d_part) {
-  switch (m) {
-#define HXV_CH_CASE(M) \
-  case M:              \
-    hipLaunchKernelGGL((ch_step_real<M, SUM, FIRST>), dim3(g), dim3(256), 0, st, n, hv, cur, prev_next, out, pr, ch, cc, cr, d_part); \
-    break;
-    HXV_CH_CASE(0)
-    HXV_CH_CASE(1)
-    HXV_CH_CASE(2)
-    HXV_CH_CASE(3)
-    HXV_CH_CASE(4)
-    HXV_CH_CASE(5)
-    HXV_CH_CASE(6)
-    HXV_CH_CASE(7)
-    HXV_CH_CASE(8)
-#undef HXV_CH_CASE
-  }
+  with_probe_count<0>(m, [&](auto M) {
+    hipLaunchKernelGGL((ch_step_real<M(), SUM, FIRST>), dim3(g), dim3(256), 0, st, n, hv, cur, prev_next, out, pr, ch, cc, cr, d_part);
+  });
 }
 // one real step on g workgroups (out null: no running sum; first: the form without t_prev), then the block-ordered sum of the partials
 inline void launch_ch_step_real(int g, hipStream_t st, int m, bool first, int64_t n, const double2* hv, const double2* cur, double2* prev_next,

@@ -61,6 +61,11 @@ void launch_to_complex(const hxv_handle* h, const double* src, double2* dst, hip
 // scal[slot] of h->d_scalars = |x|^2 (op 0) or |x| (op 1) of the n double2 elements of x, over all ranks of a split sector, enqueued on the
 // handle's stream (hxv_lanczos.hip)
 int enqueue_norm(hxv_handle* h, const double2* x, int64_t n, int slot, int op);
+// THE argument check of a probe list, for the four entries that take one (hxv_lanczos.hip): the range of nprobes, and with nprobes > 0 the list,
+// the entry's output arrays (have_outputs; `outputs` names them in the message), every entry of the list, and that no probe lies in a gather
+// buffer of the handle (why_gather: what would happen to it there).  HXV_ERR_ARG with "<who>: ..." or HXV_OK.
+int check_probe_list(const hxv_handle* h, const char* who, int nprobes, const void* const* d_probes, bool have_outputs, const char* outputs,
+                     const char* why_gather);
 // deterministic start vector of this rank's slab (a hash of the global reference index) / its real part
 void launch_init(const hxv_handle* h, double2* q, uint64_t seed, hipStream_t st);
 void launch_init_real(const hxv_handle* h, double* q, uint64_t seed, hipStream_t st);

@@ -4,6 +4,9 @@
 // hxv_ladder.hip's.)
 // Every driver -- and the local step hxv_eigh_lowest borrows -- takes its fused iteration from ONE function, fused_step_enqueue; the drivers
 // differ in who provides s and c (a host upload, or lz_next on the device), in whether there is a previous vector, and in what they read back.
+// The recurrence around it is ONE object, LzRunner, with one component or -- the paired drivers -- two, and the host-stepped loop of the single
+// and of the paired tridiagonalisation is ONE function over it (host_stepped_loop); the probes' argument check (check_probe_list) and the
+// carving of their scratch (ProbeScratch, hxv_call_scope.hpp) are shared with hxv_chebyshev.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -110,25 +113,36 @@ struct LzBuf {
 //  * plain : w = H q (any kernel), then lz_sub_dot / lz_sub_nrm / lz_scale on normalised vectors;
 //  * fused : vectors are kept UNNORMALISED (q_k = s*X, s = 1/beta_k) and go through fused_step_enqueue.
 //            144 B/state per iteration instead of 224.
+// One component, or -- the paired drivers -- two: Re and Im of the vectors are two independent real recurrences on one product, each with its
+// own scale factors, the second one's scalars LZ_PAIR behind the first one's in a block of 2*LZ_PAIR doubles the call brings.  Two components
+// exist for the fused recurrence on complex vectors only; the plain recurrence and the device-only run are single-component.
 struct LzRunner {
   hxv_handle* h;
   LzBuf b;
+  int nc;               // components
   bool fused;
   bool real;            // REAL-vector mode (see lz_len)
   int64_t n2;           // double2 elements of one vector
+  double* scal;         // the LzSlot block(s) in device memory
   bool first = true;
-  LzScale sc;           // q = sc.s_cur * b.q (fused) ; 1 (plain)
-  double last_beta = 0.0;
+  LzScale sc[2];        // q = sc[c].s_cur * (component c of b.q) (fused) ; 1 (plain)
+  bool alive[2] = {true, true};  // a component retire()d after a breakdown is multiplied away (s = c = 0): the other one goes on alone
+  double last_beta[2] = {0.0, 0.0};
 
-  LzRunner(hxv_handle* hh, double2* x, double2* xm, double2* w, bool real_vec = false)
-      : h(hh), b{x, xm, w}, fused(lanczos_local_step_available(hh)), real(real_vec), n2(lz_len(hh, real_vec)) {
-    hh->last_real = real ? 1 : 0;
+  // pair_scal: null, or the 2*LZ_PAIR scalars of a two-component run (which is fused whatever the plan: its driver has checked the option)
+  LzRunner(hxv_handle* hh, double2* x, double2* xm, double2* w, bool real_vec = false, double* pair_scal = nullptr)
+      : h(hh), b{x, xm, w}, nc(pair_scal ? 2 : 1), fused(pair_scal || lanczos_local_step_available(hh)), real(real_vec), n2(lz_len(hh, real_vec)),
+        scal(pair_scal ? pair_scal : hh->d_scalars) {
+    hh->last_real = nc == 2 ? 2 : real ? 1 : 0;
   }
 
-  // b.q holds a vector of norm `nrm` (pass 1.0 if already normalised)
-  int begin(double nrm) {
+  // b.q holds a vector of norm `nrm`, its second component one of norm `nrm_b` (pass 1.0 if already normalised)
+  int begin(double nrm, double nrm_b = 1.0) {
     first = true;
-    sc.begin(nrm);
+    sc[0].begin(nrm);
+    sc[1].begin(nrm_b);
+    alive[0] = alive[1] = true;
+    if (nc == 2 && real) return fail(HXV_ERR_STATE, "the paired Lanczos recurrence runs on complex vectors");
     if (!fused && nrm != 1.0) return fail(HXV_ERR_STATE, "plain Lanczos expects a normalised start vector");
     return HXV_OK;
   }
@@ -144,10 +158,12 @@ struct LzRunner {
     return rc ? rc : begin(1.0);
   }
 
+  // one step: alpha[c], beta[c] of every component c < nc (those of a retired one mean nothing)
   int step(double* alpha, double* beta) {
     const int64_t n = n2;
     const int g = grid_for(n);
     int rc;
+    double up[2][2], host[2 * LZ_PAIR];
     if (!fused) {
       // (apply_slab = exchange + product on a split sector, the plain product otherwise)
       rc = real ? apply_slab_real(h, (const double*)b.q, (double*)b.w, h->stream) : apply_slab(h, b.q, b.w, h->stream);
@@ -158,19 +174,28 @@ struct LzRunner {
       hipLaunchKernelGGL(lz_sub_nrm, dim3(g), dim3(256), 0, h->stream, n, b.w, b.q, h->d_scalars, LZ_ALPHA, h->d_partials + RED_BLOCKS);
       rc = reduce_scalar(h, h->d_partials + RED_BLOCKS, g, LZ_BETA, 1);
     } else {
-      const double up[2] = {sc.s_cur, first ? 0.0 : sc.c()};  // -> LZ_S, LZ_C
-      HIPCHK(hipMemcpyAsync(h->d_scalars + LZ_S, up, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      rc = fused_step_enqueue(h, real, b.q, first ? nullptr : b.qm, b.w, h->d_scalars, false);
+      for (int c = 0; c < nc; ++c) {  // -> LZ_S, LZ_C of each component
+        up[c][0] = alive[c] ? sc[c].s_cur : 0.0;
+        up[c][1] = (first || !alive[c]) ? 0.0 : sc[c].c();
+        HIPCHK(hipMemcpyAsync(scal + c * LZ_PAIR + LZ_S, up[c], 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      }
+      rc = fused_step_enqueue(h, real, b.q, first ? nullptr : b.qm, b.w, scal, nc == 2);
     }
     if (rc) return rc;
-    double host[2];
-    HIPCHK(hipMemcpyAsync(host, h->d_scalars + LZ_ALPHA, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    // one component: alpha and beta, which lie side by side; two: both blocks in one copy
+    const int lo = nc == 2 ? 0 : LZ_ALPHA, cnt = nc == 2 ? 2 * LZ_PAIR : 2;
+    HIPCHK(hipMemcpyAsync(host + lo, scal + lo, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    *alpha = host[0];
-    *beta = host[1];
-    last_beta = host[1];
+    for (int c = 0; c < nc; ++c) {
+      alpha[c] = host[c * LZ_PAIR + LZ_ALPHA];
+      beta[c] = last_beta[c] = host[c * LZ_PAIR + LZ_BETA];
+    }
     return HXV_OK;
   }
+
+  // may a fixed-length run of nmax iterations without probes hand iterations 1..nmax-1 to the device (run_device_only)?  Serial sectors: the
+  // all-reduces of a split one go through the host loop.
+  bool device_only_ok(int nmax) const { return nc == 1 && fused && h->lz_graph && nmax >= 8 && !comm_ready(h); }
 
   // Iterations 1..nmax-1 of a fixed-length run on the device alone (after the hand-over of run_device_only): each one is the fused step on the
   // scalars lz_next left, then lz_next; alpha/beta go to device arrays.  The three-iteration pointer-rotation cycle is captured ONCE into a
@@ -230,11 +255,12 @@ struct LzRunner {
   // hxv_time_lanczos's pair): ev[0] is recorded after the hand-over and before the first captured iteration, ev[1]
   // after the last one, and waited for.
   int run_device_only(double beta, int nmax, double* ab, hipEvent_t* ev, const char* who) {
+    if (nc != 1) return fail(HXV_ERR_STATE, std::string(who) + ": the device-only run is single-component");
     CallScope scratch(h);
     double* d_ab = nullptr;
     HIPCHK(scratch.take_device((size_t)2 * nmax * sizeof(double), &d_ab));
     HIPCHK(hipMemsetAsync(d_ab, 0, (size_t)2 * nmax * sizeof(double), h->stream));
-    const double s1 = 1.0 / beta, bprev = 1.0 / sc.s_cur;
+    const double s1 = 1.0 / beta, bprev = 1.0 / sc[0].s_cur;
     const double init[2] = {s1, 1.0 / (s1 * bprev)};   // s_1 = 1/beta_1 ; c_1 = beta_1/beta_0, rounded like LzScale::next() + c()
     const double one = 1.0;
     hipError_t e = hipMemcpyAsync(h->d_scalars + LZ_S, init, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
@@ -269,15 +295,19 @@ struct LzRunner {
       b.qm = b.q;      // X_{k-1}
       b.q = b.w;       // X_k = unnormalised residual
       b.w = old_m;
-      sc.next(last_beta);
+      for (int c = 0; c < nc; ++c)
+        if (alive[c]) sc[c].next(last_beta[c]);
     }
     first = false;
     return HXV_OK;
   }
+  // component c's Krylov space has closed: it makes no further step
+  void retire(int c) { alive[c] = false; }
+  bool any_alive() const { return alive[0] || (nc == 2 && alive[1]); }
 
-  // current normalised Lanczos vector = scale() * vec()
+  // current normalised Lanczos vector = scale() * vec(), per component
   const double2* vec() const { return b.q; }
-  double scale() const { return fused ? sc.s_cur : 1.0; }
+  double scale(int c = 0) const { return fused ? sc[c].s_cur : 1.0; }
 };
 
 // the three work vectors of the single-vector Lanczos; `real` = layout of the coming run.  The pad rows of the two
@@ -326,11 +356,77 @@ int stage_start_vector(hxv_handle* h, const void*& d_vin, CallScope& pooled) {
   return HXV_OK;
 }
 
-// out[2*j], out[2*j+1] = Re, Im <p_j|x> of this rank's share (n double2 elements), j < m, on the handle's stream (the kernels and the dispatch on
-// m: hxv_lanczos_kernels.hpp).  d_part: grid_for(n) * 2m doubles.
-template <bool REAL>
-void launch_probe_dots(hxv_handle* h, int m, int64_t n, const double2* x, const LzProbes& pr, double* d_part, double* d_out) {
-  launch_probe_dots<REAL>(grid_for(n), h->stream, m, n, x, pr, d_part, d_out);
+// The probes of a run and where their overlaps go: which kernel takes the overlaps of a stored vector (lz_probe_dots<M, REAL> on complex or real
+// vectors, or -- `pair` -- lz_probe_dots_pair<M> with the real probes shared by both components) and how the 2*m sums of a step map to a
+// component's row of the caller's overlaps array.  m = 0: no probes, nothing is launched.  part, sums: ProbeScratch's.
+struct LzProbeSet {
+  int m = 0;
+  bool real = false, pair = false;
+  LzProbes pr{};       // single runs: complex vectors, or real ones viewed as double2
+  LzRealProbes rp{};   // paired runs
+  double *part = nullptr, *sums = nullptr;
+  // sums[2*m] = the overlaps of x (n double2 elements of this rank) with the probes: ONE all-reduce for them on a split sector
+  int enqueue(hxv_handle* h, int64_t n, const double2* x) const {
+    if (pair)
+      launch_probe_dots_pair(grid_for(n), h->stream, m, n, x, rp, part, sums);
+    else if (real)
+      launch_probe_dots<true>(grid_for(n), h->stream, m, n, x, pr, part, sums);
+    else
+      launch_probe_dots<false>(grid_for(n), h->stream, m, n, x, pr, part, sums);
+    return comm_allreduce_sum(h, sums, (size_t)2 * m, h->stream);
+  }
+  // ov[2*m] of component c: the staged sums times s.  Single: (Re, Im) <p_j|x> as they lie.  Paired: the sums are <p_j|Re x>, <p_j|Im x>; component
+  // c's go to the real slots, the imaginary ones stay the zeros the driver wrote.
+  void store(const double* stage, int c, double s, double* ov) const {
+    if (pair)
+      for (int j = 0; j < m; ++j) ov[2 * j] = stage[2 * j + c] * s;
+    else
+      for (int j = 0; j < 2 * m; ++j) ov[j] = stage[j] * s;
+  }
+};
+
+// what a tridiagonalisation returns per component: alanc[nlanc], blanc[nlanc], overlaps[2*nlanc*m] (null without probes), nsteps
+struct LzOut {
+  double *al, *bl, *ov;
+  int nsteps = 0;
+  void clear(int nlanc, int m) const {
+    for (int k = 0; k < nlanc; ++k) al[k] = bl[k] = 0.0;
+    for (size_t i = 0; i < (size_t)2 * nlanc * m; ++i) ov[i] = 0.0;
+  }
+};
+
+// THE host-stepped loop of both tridiagonalisation drivers, over a runner that has begun: per step the overlaps of the STORED vector X_k,
+// enqueued before the step that overwrites nothing of it -- one all-reduce, one copy into this step's slot of h->h_probe_ov (a slot per step:
+// nothing is overwritten while a copy is in flight), which completes with the synchronisation step() makes for alpha and beta --, then the
+// step, then per live component alpha, beta and the overlaps of q_k = s * X_k with the s of BEFORE the step, the breakdown rule, and the
+// rotation.  out[c].nsteps = the steps component c made.
+int host_stepped_loop(hxv_handle* h, LzRunner& lz, const LzProbeSet& pb, int nlanc, double threshold, LzOut* out) {
+  const int m = pb.m;
+  for (int k = 0; k < nlanc && lz.any_alive(); ++k) {
+    double* stage = m > 0 ? h->h_probe_ov + (size_t)2 * m * k : nullptr;
+    if (m > 0) {
+      int rc = pb.enqueue(h, lz.n2, lz.vec());
+      if (rc) return rc;
+      HIPCHK(hipMemcpyAsync(stage, pb.sums, (size_t)2 * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    const double s[2] = {lz.scale(0), lz.scale(1)};
+    double a[2], bt[2];
+    int rc = lz.step(a, bt);
+    if (rc) return rc;
+    for (int c = 0; c < lz.nc; ++c) {
+      if (!lz.alive[c]) continue;
+      if (m > 0) pb.store(stage, c, s[c], out[c].ov + (size_t)2 * m * k);
+      out[c].al[k] = a[c];
+      if (k + 1 < nlanc) out[c].bl[k + 1] = bt[c];
+      out[c].nsteps = k + 1;
+      // breakdown of this component's Krylov space.  The paired run also retires a component whose beta is not finite, so that the other one
+      // goes on; the single run has no other one and, as sp_lanc_tridiag does, goes on to nlanc.
+      if (std::fabs(bt[c]) < threshold || (lz.nc == 2 && !std::isfinite(bt[c]))) lz.retire(c);
+    }
+    // (not after the last step: the plain recurrence's advance() launches a kernel)
+    if (k + 1 < nlanc && lz.any_alive() && (rc = lz.advance())) return rc;
+  }
+  return HXV_OK;
 }
 
 }  // namespace
@@ -356,6 +452,17 @@ bool want_real(const hxv_handle* h) { return h->real_vectors && !real_mode_block
 int need_comm(const hxv_handle* h, const char* who) {
   if (h->host.nranks == 1 || comm_ready(h)) return HXV_OK;
   return fail(HXV_ERR_STATE, std::string(who) + " on a split sector needs the communicator: call hxv_comm_init after opening the sector");
+}
+int check_probe_list(const hxv_handle* h, const char* who, int nprobes, const void* const* d_probes, bool have_outputs, const char* outputs,
+                     const char* why_gather) {
+  const std::string w = std::string(who) + ": ";
+  if (nprobes < 0 || nprobes > HXV_MAX_PROBES) return fail(HXV_ERR_ARG, w + "nprobes must be 0 .. HXV_MAX_PROBES (8)");
+  if (nprobes > 0 && (!d_probes || !have_outputs)) return fail(HXV_ERR_ARG, w + "nprobes > 0 needs the probe list and " + outputs);
+  for (int j = 0; j < nprobes; ++j) {
+    if (!d_probes[j]) return fail(HXV_ERR_ARG, w + "NULL entry in the probe list");
+    if (comm_ready(h) && comm_in_gather(h, d_probes[j])) return fail(HXV_ERR_ARG, w + "a probe lies in a gather buffer of the handle (hxv_slab_home): " + why_gather);
+  }
+  return HXV_OK;
 }
 // may this handle use the fused product?  (split sectors included: the epilogue's partial sums are this rank's share, alpha and beta are
 // all-reduced.)  When not, the drivers run the plain recurrence and hxv_eigh_lowest measures its two local projections itself.
@@ -400,23 +507,18 @@ namespace {
 int tridiag_run(hxv_handle* h, const char* who, int rc_args, const void* d_vin, int nprobes, const void* const* d_probes, int nlanc,
                 double* alanc, double* blanc, double* overlaps, double threshold, int32_t* nsteps) {
   HIPCHK(hipSetDevice(h->device));  // (before the first collective: thread ranks on several GPUs each have their own current device)
-  // scratch of a run WITH probes, from the device-buffer cache and sized by nprobes: block partials of the real-vector check (start vector and
-  // probes, side by side), block partials and sums of a step's overlaps.  Without probes the check's partials are the handle's own.
-  double* d_ws = nullptr;
+  // scratch of a run WITH probes (ProbeScratch): the real-vector check's partials are a row of RED_BLOCKS for the start vector and one per probe,
+  // side by side; a slot of 2*nprobes staged sums per step.  Without probes the check's partials are the handle's own.
+  ProbeScratch ws;
   CallScope pooled(h);  // (with the staged start vector and the real-mode copies of the probes)
-  size_t n_chk = 0, n_part = 0;
   // what a rank decides from its own arguments and resources, agreed on before the first collective
   auto resources = [&]() -> int {
     if (rc_args || nprobes == 0) return rc_args;
-    n_chk = (size_t)(1 + nprobes) * RED_BLOCKS;
-    n_part = (size_t)2 * nprobes * RED_BLOCKS;
-    HIPCHK(pooled.take((n_chk + n_part + 2 * nprobes) * sizeof(double), &d_ws));
-    // page-locked staging for the overlaps of every step: a copy into the caller's pageable array could make the runtime wait per step
-    return ensure_probe_stage(h, (int64_t)2 * nprobes * nlanc);
+    return ws.take(h, pooled, (size_t)(1 + nprobes) * RED_BLOCKS, (size_t)2 * nprobes * RED_BLOCKS, (size_t)2 * nprobes, (int64_t)2 * nprobes * nlanc);
   };
   if (int rca = comm_agree(h, resources())) return rca;
   if (int rcc = need_comm(h, "device Lanczos")) return rcc;
-  double *d_chk = nprobes ? d_ws : h->d_partials, *d_part = d_ws + n_chk, *d_ov = d_part + n_part;
+  double* d_chk = nprobes ? ws.chk : h->d_partials;
   const int64_t n = (int64_t)h->host.pitch * h->host.qdw;  // this rank's slab
   const size_t real_bytes = (size_t)pitch_real_of(h) * std::max(h->host.qdw, 1) * sizeof(double);
   double* real_probe[HXV_MAX_PROBES] = {};
@@ -448,10 +550,14 @@ int tridiag_run(hxv_handle* h, const char* who, int rc_args, const void* d_vin, 
   int rc = comm_agree(h, prepare());  // (a rank that could not allocate tells its peers before the first all-reduce)
   if (rc) return rc;
   LzRunner lz(h, h->lz_vec[0], h->lz_vec[1], h->lz_vec[2], real);
-  LzProbes pr{};
+  LzProbeSet pb;
+  pb.m = nprobes;
+  pb.real = real;
+  pb.part = ws.part;
+  pb.sums = ws.sums;
   for (int j = 0; j < nprobes; ++j) {
     if (real) launch_to_real(h, (const double2*)d_probes[j], real_probe[j], h->stream);
-    pr.p[j] = real ? (const double2*)real_probe[j] : (const double2*)d_probes[j];
+    pb.pr.p[j] = real ? (const double2*)real_probe[j] : (const double2*)d_probes[j];
   }
   if (real)
     launch_to_real(h, (const double2*)d_vin, (double*)lz.b.q, h->stream);
@@ -472,16 +578,15 @@ int tridiag_run(hxv_handle* h, const char* who, int rc_args, const void* d_vin, 
     rc = lz.begin(nrm);
   }
   if (rc) return rc;
-  for (int k = 0; k < nlanc; ++k) alanc[k] = blanc[k] = 0.0;
-  for (size_t i = 0; i < (size_t)2 * nlanc * nprobes; ++i) overlaps[i] = 0.0;
-  int k = 0;
-  if (nprobes == 0 && lz.fused && h->lz_graph && nlanc >= 8 && !comm_ready(h)) {  // (device-only iterations: serial sectors; the all-reduces of a split one go through the host loop)
+  LzOut out{alanc, blanc, overlaps};
+  out.clear(nlanc, nprobes);
+  if (nprobes == 0 && lz.device_only_ok(nlanc)) {
     // Fixed-length run without probes (the Green's-function use, ED_GF_NORMAL.f90:204-220): iteration 0 with the host in the loop, the other
     // nlanc-1 on the device alone -- scalars stay in device memory, the pointer-rotation cycle of three iterations is one hipGraph -- and
     // alpha/beta come back once at the end.  A breakdown (beta < threshold) is found afterwards; whatever was computed past it is discarded.
     rc = lz.step(&alanc[0], &blanc[1]);
     if (rc) return rc;
-    k = 1;
+    int k = 1;
     if (std::fabs(blanc[1]) >= threshold) {
       std::vector<double> ab((size_t)2 * nlanc, 0.0);
       rc = lz.run_device_only(blanc[1], nlanc, ab.data(), nullptr, who);
@@ -498,40 +603,12 @@ int tridiag_run(hxv_handle* h, const char* who, int rc_args, const void* d_vin, 
         }
       }
     }
-  } else {
-    for (; k < nlanc; ++k) {
-      double* ov = nprobes > 0 ? overlaps + (size_t)2 * nprobes * k : nullptr;
-      double* stage = nprobes > 0 ? h->h_probe_ov + (size_t)2 * nprobes * k : nullptr;  // (a slot per step: nothing is overwritten while a copy is in flight)
-      if (nprobes > 0) {
-        // the overlaps of the STORED vector X_k, enqueued before the step that overwrites nothing of it; their copy to the host completes with
-        // the synchronisation step() makes for alpha and beta.  One all-reduce for the 2*nprobes sums of a split sector.
-        if (real)
-          launch_probe_dots<true>(h, nprobes, lz.n2, lz.vec(), pr, d_part, d_ov);
-        else
-          launch_probe_dots<false>(h, nprobes, lz.n2, lz.vec(), pr, d_part, d_ov);
-        rc = comm_allreduce_sum(h, d_ov, (size_t)2 * nprobes, h->stream);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(stage, d_ov, (size_t)2 * nprobes * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      }
-      const double s = lz.scale();  // q_k = s * X_k
-      double a, bt;
-      rc = lz.step(&a, &bt);
-      if (rc) return rc;
-      for (int j = 0; j < 2 * nprobes; ++j) ov[j] = stage[j] * s;
-      alanc[k] = a;
-      if (k + 1 < nlanc) blanc[k + 1] = bt;
-      if (std::fabs(bt) < threshold) {
-        ++k;
-        break;
-      }
-      if (k + 1 < nlanc) {
-        rc = lz.advance();
-        if (rc) return rc;
-      }
-    }
+    out.nsteps = k;
+  } else if ((rc = host_stepped_loop(h, lz, pb, nlanc, threshold, &out))) {
+    return rc;
   }
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (nsteps) *nsteps = k;
+  if (nsteps) *nsteps = out.nsteps;
   return HXV_OK;
 }
 }  // namespace
@@ -552,14 +629,8 @@ int hxv_lanczos_tridiag_probes(hxv_handle* h, const void* d_vin, int32_t nprobes
   if (!h) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: NULL handle");
   auto check_args = [&]() -> int {
     if (!d_vin || nlanc < 1 || !alanc || !blanc || !nsteps) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: bad argument (NULL start vector or output, or nlanc < 1)");
-    if (nprobes < 0 || nprobes > HXV_MAX_PROBES) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: nprobes must be 0 .. HXV_MAX_PROBES (8)");
-    if (nprobes > 0 && (!d_probes || !overlaps)) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: nprobes > 0 needs the probe list and the overlaps array");
-    for (int j = 0; j < nprobes; ++j) {
-      if (!d_probes[j]) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: NULL entry in the probe list");
-      // (ensure_lz clears the slab's place in the gather buffers; a START vector there is staged, a probe is the caller's to keep elsewhere)
-      if (comm_ready(h) && comm_in_gather(h, d_probes[j])) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_probes: a probe lies in a gather buffer of the handle (hxv_slab_home): the driver clears that place");
-    }
-    return HXV_OK;
+    // (ensure_lz clears the slab's place in the gather buffers; a START vector there is staged, a probe is the caller's to keep elsewhere)
+    return check_probe_list(h, "hxv_lanczos_tridiag_probes", nprobes, d_probes, overlaps != nullptr, "the overlaps array", "the driver clears that place");
   };
   return tridiag_run(h, "hxv_lanczos_tridiag_probes", check_args(), d_vin, nprobes, d_probes, nlanc, alanc, blanc, overlaps, threshold, nsteps);
 }
@@ -605,31 +676,23 @@ int hxv_lanczos_eigh(hxv_handle* h, int32_t nitermax, double threshold, double* 
   LzRunner lz(h, h->lz_vec[0], h->lz_vec[1], h->lz_vec[2], real);
   rc = lz.begin_own(seed);
   if (rc) return rc;
-  std::vector<double> al, be(1, 0.0);
+  std::vector<double> al, be(1, 0.0), y;
   double e_old = 1e300, e_new = 0;
   int k = 0;
-  std::vector<double> d, e;
   for (; k < nmax; ++k) {
     double a, bt;
     rc = lz.step(&a, &bt);
     if (rc) return rc;
     al.push_back(a);
-    d = al;
-    e = be;
-    if (!tridiag_ql((int)d.size(), d, e, nullptr)) return fail(HXV_ERR_STATE, "tridiagonal QL did not converge");
-    e_new = *std::min_element(d.begin(), d.end());
+    if (!lowest_ritz(al, be, &e_new, nullptr)) return fail(HXV_ERR_STATE, "tridiagonal QL did not converge");
     bool conv = std::fabs(e_new - e_old) < threshold;
     e_old = e_new;
     if (conv && d_vect) {
       // the energy converges quadratically faster than the vector: before accepting, require the Ritz
       // residual estimate |beta_{k+1} * y_k| (last component of the tridiagonal eigenvector) to be small too
-      const int m = (int)al.size();
-      std::vector<double> dd = al, ee = be, zz((size_t)m * m, 0.0);
-      ee.resize(m, 0.0);
-      for (int i = 0; i < m; ++i) zz[i + (size_t)i * m] = 1.0;
-      if (!tridiag_ql(m, dd, ee, &zz)) return fail(HXV_ERR_STATE, "tridiagonal QL did not converge");
-      int jm = (int)(std::min_element(dd.begin(), dd.end()) - dd.begin());
-      const double resid = std::fabs(bt * zz[(size_t)(m - 1) + (size_t)jm * m]);
+      double e_y;
+      if (!lowest_ritz(al, be, &e_y, &y)) return fail(HXV_ERR_STATE, "tridiagonal QL did not converge");
+      const double resid = std::fabs(bt * y.back());
       conv = resid < 1e-11 * std::max(1.0, std::fabs(e_new));
     }
     if (conv || std::fabs(bt) < 1e-14 || k + 1 == nmax) {
@@ -645,14 +708,8 @@ int hxv_lanczos_eigh(hxv_handle* h, int32_t nitermax, double threshold, double* 
   if (d_vect) {
     // second pass: re-run the recurrence and accumulate the Ritz vector sum_j y_j q_j
     const int m = (int)al.size();
-    d = al;
-    e = be;
-    e.resize(m, 0.0);
-    std::vector<double> z((size_t)m * m, 0.0);
-    for (int i = 0; i < m; ++i) z[i + (size_t)i * m] = 1.0;
-    if (!tridiag_ql(m, d, e, &z)) return fail(HXV_ERR_STATE, "tridiagonal QL did not converge");
-    int jmin = (int)(std::min_element(d.begin(), d.end()) - d.begin());
-    const double* y = &z[(size_t)jmin * m];
+    double e_y;
+    if (!lowest_ritz(al, be, &e_y, &y)) return fail(HXV_ERR_STATE, "tridiagonal QL did not converge");
     double2* out = (double2*)d_vect;
     LzRunner lz2(h, h->lz_vec[0], h->lz_vec[1], h->lz_vec[2], real);
     rc = lz2.begin_own(seed);
@@ -686,7 +743,8 @@ namespace {
 // complex vector -- H(x + i y) = H x + i H y -- and every scalar of the recurrence exists once per component.  The channels of
 // one Green's-function solve are independent (ED_GF_NORMAL.f90:123-306: one sp_lanc_tridiag per channel), so two of them share
 // the product's passes.  The arithmetic of each component is, operation for operation, that of hxv_lanczos_tridiag on (x, 0)
-// through the same kernels (options real_vectors = 0, job_up = 0): alanc/blanc are bit-identical to two such runs.
+// through the same kernels (options real_vectors = 0, job_up = 0): alanc/blanc are bit-identical to two such runs -- after the start-up
+// below the recurrence is tridiag_run's own code, a two-component LzRunner in host_stepped_loop.
 // With probes (real ones, shared by both components; converted once into pooled double[qdw][pitch] buffers) the overlaps of the STORED
 // complex vector are taken before each step's product, as in tridiag_run, by lz_probe_dots_pair: overlaps_x as hxv_lanczos_tridiag_probes
 // lays them out, imaginary parts zero.  rc_args: what the entry decided from its own arguments; it goes into the agreement in front of the
@@ -704,11 +762,12 @@ int tridiag_pair_run(hxv_handle* h, const char* who, int rc_args, const void* d_
   // scalars: the LzSlot block of component a, the one of b LZ_PAIR behind it (the handle's d_scalars has room for one only); the block
   // partials of the start vectors' check behind them
   double* d_sc_mem = nullptr;
-  // scratch of a run WITH probes, from the device-buffer cache and sized by nprobes: block partials of Im^2 (start vectors, then one row of
-  // RED_BLOCKS per probe, g of each used, side by side for the one reduction), block partials and sums of a step's overlaps
-  double* d_ws = nullptr;
-  const size_t n_chk = (size_t)(1 + std::max(nprobes, 0)) * RED_BLOCKS, n_part = (size_t)2 * std::max(nprobes, 0) * RED_BLOCKS;
-  LzRealProbes pr{};
+  // scratch of a run WITH probes (ProbeScratch): the partials of Im^2 are the start vectors' row, then one row of RED_BLOCKS per probe, g of each
+  // used, side by side for the one reduction
+  ProbeScratch ws;
+  LzProbeSet pb;
+  pb.m = std::max(nprobes, 0);
+  pb.pair = true;
   // every rank-local preparation that can fail comes BEFORE the agreement: a rank that cannot go on makes all ranks return
   auto prepare = [&]() -> int {
     if (rc_args) return rc_args;
@@ -720,24 +779,23 @@ int tridiag_pair_run(hxv_handle* h, const char* who, int rc_args, const void* d_
     if (r) return r;
     HIPCHK(pooled.take_device((size_t)(2 * LZ_PAIR + 3 * RED_BLOCKS) * sizeof(double), &d_sc_mem));
     if (nprobes == 0) return HXV_OK;
-    HIPCHK(pooled.take((n_chk + n_part + 2 * nprobes) * sizeof(double), &d_ws));
-    for (int j = 0; j < nprobes; ++j) HIPCHK(pooled.take((size_t)std::max<int64_t>(n, 1) * sizeof(double), &pr.p[j]));
-    // page-locked staging for the overlaps of every step (a slot of 2*nprobes sums per step), shared with tridiag_run
-    return ensure_probe_stage(h, (int64_t)2 * nprobes * nlanc);
+    r = ws.take(h, pooled, (size_t)(1 + nprobes) * RED_BLOCKS, (size_t)2 * nprobes * RED_BLOCKS, (size_t)2 * nprobes, (int64_t)2 * nprobes * nlanc);
+    for (int j = 0; j < nprobes && !r; ++j) HIPCHK(pooled.take((size_t)std::max<int64_t>(n, 1) * sizeof(double), &pb.rp.p[j]));
+    return r;
   };
   int rc = comm_agree(h, prepare());
   if (rc) return rc;
   double* const d_sc = d_sc_mem;
-  double* d_p0 = nprobes ? d_ws : d_sc + 2 * LZ_PAIR;  // (Im^2 of the start vectors; the probes' rows follow it at a distance of g)
+  double* d_p0 = nprobes ? ws.chk : d_sc + 2 * LZ_PAIR;  // (Im^2 of the start vectors; the probes' rows follow it at a distance of g)
   double* d_p1 = d_sc + 2 * LZ_PAIR + RED_BLOCKS;
   double* d_p2 = d_p1 + RED_BLOCKS;
-  double *d_part = d_ws + n_chk, *d_ov = d_part + n_part;
+  pb.part = ws.part;
+  pb.sums = ws.sums;
   HIPCHK(hipMemsetAsync(d_sc, 0, 2 * LZ_PAIR * sizeof(double), h->stream));
-  double2 *q = h->lz_vec[0], *qm = h->lz_vec[1], *w = h->lz_vec[2];
-  hipLaunchKernelGGL(lz_pack_pair, dim3(g), dim3(256), 0, h->stream, n, (const double2*)d_vin_a, (const double2*)d_vin_b, q, d_p0, d_p1, d_p2);
+  hipLaunchKernelGGL(lz_pack_pair, dim3(g), dim3(256), 0, h->stream, n, (const double2*)d_vin_a, (const double2*)d_vin_b, h->lz_vec[0], d_p0, d_p1, d_p2);
   for (int j = 0; j < nprobes; ++j)
     hipLaunchKernelGGL(lz_probe_real_pc, dim3(g), dim3(256), 0, h->stream, n, h->host.dimup, h->host.pitch, (const double2*)d_probes[j],
-                       const_cast<double*>(pr.p[j]), d_p0 + (size_t)(1 + j) * g);
+                       const_cast<double*>(pb.rp.p[j]), d_p0 + (size_t)(1 + j) * g);
   // (its own block: the three sums of the check sit in a row from LZ_TMP on)
   if ((rc = reduce_scalar(h, d_p0, (1 + nprobes) * g, LZ_TMP, 0, d_sc)) || (rc = reduce_scalar(h, d_p1, g, LZ_TMP + 1, 1, d_sc)) || (rc = reduce_scalar(h, d_p2, g, LZ_TMP + 2, 1, d_sc))) return rc;
   double head[3];
@@ -748,63 +806,14 @@ int tridiag_pair_run(hxv_handle* h, const char* who, int rc_args, const void* d_
     return fail(HXV_ERR_ARG, std::string(who) + (nprobes ? ": the start vectors and the probes must be real (zero imaginary parts)" : ": the start vectors must be real (zero imaginary parts)"));
   for (int c = 0; c < 2; ++c)
     if (!(head[1 + c] > 0.0) || !std::isfinite(head[1 + c])) return fail(HXV_ERR_ARG, std::string(who) + ": a start vector is zero or not finite");
-  for (int k = 0; k < nlanc; ++k) alanc_a[k] = blanc_a[k] = alanc_b[k] = blanc_b[k] = 0.0;
-  for (size_t i = 0; i < (size_t)2 * nlanc * nprobes; ++i) overlaps_a[i] = overlaps_b[i] = 0.0;
-  // per component, LzRunner's fused recurrence: q = s*X, s = 1/beta_k (the start vector's norm carried as beta_0)
-  LzScale scale[2];
-  bool alive[2] = {true, true};
-  int done[2] = {0, 0};
-  for (int c = 0; c < 2; ++c) scale[c].begin(start_norm(head[1 + c]));
-  double* al[2] = {alanc_a, alanc_b};
-  double* bl[2] = {blanc_a, blanc_b};
-  double* ovl[2] = {overlaps_a, overlaps_b};
-  bool first = true;
-  for (int k = 0; k < nlanc && (alive[0] || alive[1]); ++k) {
-    const double* stage = nullptr;
-    if (nprobes > 0) {
-      // the overlaps of the STORED vector X_k, enqueued before the step that overwrites nothing of it; their copy to the host completes with
-      // the synchronisation the step makes for alpha and beta.  One all-reduce for the 2*nprobes sums of a split sector.
-      double* slot = h->h_probe_ov + (size_t)2 * nprobes * k;  // (a slot per step: nothing is overwritten while a copy is in flight)
-      launch_probe_dots_pair(g, h->stream, nprobes, n, q, pr, d_part, d_ov);
-      if ((rc = comm_allreduce_sum(h, d_ov, (size_t)2 * nprobes, h->stream))) return rc;
-      HIPCHK(hipMemcpyAsync(slot, d_ov, (size_t)2 * nprobes * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      stage = slot;
-    }
-    double up[2][2];  // -> LZ_S, LZ_C of each component (a finished one is multiplied away: the other one goes on alone)
-    for (int c = 0; c < 2; ++c) {
-      up[c][0] = alive[c] ? scale[c].s_cur : 0.0;
-      up[c][1] = (first || !alive[c]) ? 0.0 : scale[c].c();
-      HIPCHK(hipMemcpyAsync(d_sc + c * LZ_PAIR + LZ_S, up[c], 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    }
-    if ((rc = fused_step_enqueue(h, false, q, first ? nullptr : qm, w, d_sc, true))) return rc;
-    double host[2 * LZ_PAIR];
-    HIPCHK(hipMemcpyAsync(host, d_sc, sizeof(host), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (int c = 0; c < 2; ++c) {
-      if (!alive[c]) continue;
-      // q_k = s * X_k with the s of BEFORE the step (up[c][0]); the imaginary slots stay zero
-      for (int j = 0; j < nprobes; ++j) ovl[c][2 * ((size_t)k * nprobes + j)] = stage[2 * j + c] * up[c][0];
-      const double a = host[c * LZ_PAIR + LZ_ALPHA], bt = host[c * LZ_PAIR + LZ_BETA];
-      al[c][k] = a;
-      if (k + 1 < nlanc) bl[c][k + 1] = bt;
-      done[c] = k + 1;
-      if (std::fabs(bt) < threshold || !std::isfinite(bt)) {
-        alive[c] = false;  // breakdown of this component's Krylov space (the early exit of hxv_lanczos_tridiag)
-        continue;
-      }
-      scale[c].next(bt);
-    }
-    // rotate: X_{k+1} = w (unnormalised residual), X_k = q, the old X_{k-1} becomes the next output
-    double2* old_m = qm;
-    qm = q;
-    q = w;
-    w = old_m;
-    first = false;
-  }
+  LzOut out[2] = {{alanc_a, blanc_a, overlaps_a}, {alanc_b, blanc_b, overlaps_b}};
+  for (const LzOut& o : out) o.clear(nlanc, nprobes);
+  // the two-component runner on the packed vector: q = s*X per component, s = 1/beta_k (each start vector's norm carried as its beta_0)
+  LzRunner lz(h, h->lz_vec[0], h->lz_vec[1], h->lz_vec[2], false, d_sc);
+  if ((rc = lz.begin(start_norm(head[1]), start_norm(head[2]))) || (rc = host_stepped_loop(h, lz, pb, nlanc, threshold, out))) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->last_real = 2;
-  if (nsteps_a) *nsteps_a = done[0];
-  if (nsteps_b) *nsteps_b = done[1];
+  if (nsteps_a) *nsteps_a = out[0].nsteps;
+  if (nsteps_b) *nsteps_b = out[1].nsteps;
   return HXV_OK;
 }
 }  // namespace
@@ -825,14 +834,7 @@ int hxv_lanczos_tridiag_pair_probes(hxv_handle* h, const void* d_vin_a, const vo
   auto check_args = [&]() -> int {
     if (!d_vin_a || !d_vin_b || nlanc < 1 || !alanc_a || !blanc_a || !alanc_b || !blanc_b)
       return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair_probes: bad argument (NULL start vector or output, or nlanc < 1)");
-    if (nprobes < 0 || nprobes > HXV_MAX_PROBES) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair_probes: nprobes must be 0 .. HXV_MAX_PROBES (8)");
-    if (nprobes > 0 && (!d_probes || !overlaps_a || !overlaps_b)) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair_probes: nprobes > 0 needs the probe list and both overlaps arrays");
-    for (int j = 0; j < nprobes; ++j) {
-      if (!d_probes[j]) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair_probes: NULL entry in the probe list");
-      // (ensure_lz clears the slab's place in the gather buffers; a START vector there is staged, a probe is the caller's to keep elsewhere)
-      if (comm_ready(h) && comm_in_gather(h, d_probes[j])) return fail(HXV_ERR_ARG, "hxv_lanczos_tridiag_pair_probes: a probe lies in a gather buffer of the handle (hxv_slab_home): the driver clears that place");
-    }
-    return HXV_OK;
+    return check_probe_list(h, "hxv_lanczos_tridiag_pair_probes", nprobes, d_probes, overlaps_a && overlaps_b, "both overlaps arrays", "the driver clears that place");
   };
   return tridiag_pair_run(h, "hxv_lanczos_tridiag_pair_probes", check_args(), d_vin_a, d_vin_b, nprobes, d_probes, nlanc, alanc_a, blanc_a,
                           overlaps_a, alanc_b, blanc_b, overlaps_b, threshold, nsteps_a, nsteps_b);
@@ -902,7 +904,7 @@ int hxv_time_lanczos(hxv_handle* h, void* d_work3, int32_t nrep, float* ms_per_i
   double a, bt;
   rc = lz.step(&a, &bt);  // untimed first step (lazy allocations)
   if (rc) return rc;
-  if (lz.fused && h->lz_graph && nrep >= 8 && !comm_ready(h)) {
+  if (lz.device_only_ok(nrep)) {
     // the fixed-length device-only path of hxv_lanczos_tridiag: iterations 1..nrep, three per hipGraph
     hipEvent_t ev[2] = {h->ev0, h->ev1};
     rc = lz.run_device_only(bt, nrep + 1, nullptr, ev, "hxv_time_lanczos");

@@ -1,10 +1,11 @@
-// The host routines of the Lanczos drivers (hxv_lanczos.hip): the eigen-solver of the tridiagonal matrix, the host's copy of the fused
-// recurrence's scale factors and the rule for the norm a recurrence starts from.  Host C++ only, no HIP: the header lives apart so that
+// The host routines of the Lanczos drivers (hxv_lanczos.hip): the eigen-solver of the tridiagonal matrix, the lowest Ritz pair taken from it,
+// the host's copy of the fused recurrence's scale factors and the rule for the norm a recurrence starts from.  Host C++ only, no HIP: the header lives apart so that
 // tests/host/lanczos_host_check.cpp can compile it with a plain host compiler, under sanitizers, and
 // tests/device/lanczos_kernels_check.hip can set LzScale beside lz_next.  Anonymous namespace: each including file gets its own copy,
 // exactly as when the text stood in hxv_lanczos.hip.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <vector>
@@ -62,6 +63,25 @@ bool tridiag_ql(int n, std::vector<double>& d, std::vector<double>& e, std::vect
       }
     } while (m != l);
   }
+  return true;
+}
+
+// The lowest Ritz pair of a Lanczos matrix: al[m] its diagonal, be its sub-diagonal as the drivers keep it (be[0] unused, be[i] couples i - 1
+// and i; entries be does not have are zero).  -> false when the QL iteration did not converge.  *e_min: the lowest eigenvalue, *j_min (may be
+// null) its index in tridiag_ql's order (the first of equal ones); y (may be null: eigenvalues only) its eigenvector, m entries.
+inline bool lowest_ritz(const std::vector<double>& al, const std::vector<double>& be, double* e_min, std::vector<double>* y, int* j_min = nullptr) {
+  const int m = (int)al.size();
+  std::vector<double> d = al, e = be, z;
+  e.resize(m, 0.0);
+  if (y) {
+    z.assign((size_t)m * m, 0.0);
+    for (int i = 0; i < m; ++i) z[i + (size_t)i * m] = 1.0;
+  }
+  if (!tridiag_ql(m, d, e, y ? &z : nullptr)) return false;
+  const int j = (int)(std::min_element(d.begin(), d.end()) - d.begin());
+  *e_min = d[j];
+  if (j_min) *j_min = j;
+  if (y) y->assign(z.begin() + (size_t)j * m, z.begin() + (size_t)(j + 1) * m);
   return true;
 }
 

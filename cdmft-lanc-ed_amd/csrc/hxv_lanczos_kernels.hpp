@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "hxv_handle.hpp"  // RED_BLOCKS, the LzSlot indices, HXV_MAX_PROBES (include/hxv.h)
 
@@ -386,46 +387,29 @@ __global__ void lz_next(double* scal, double* alpha_out, double* beta_out, int n
   scal[LZ_STEP] = (double)(k + 1);
 }
 
+// THE dispatch on a number of probes known at run time: f(std::integral_constant<int, M>{}) for M = m when LO <= m <= HXV_MAX_PROBES, nothing
+// otherwise (the launchers below and of the Chebyshev headers then launch their final kernel alone).  LO: 1 for kernels that need a probe, 0
+// for those that run without.
+template <int LO, int M = LO, typename F>
+void with_probe_count(int m, F&& f) {
+  if (m == M)
+    f(std::integral_constant<int, M>{});
+  else if constexpr (M < HXV_MAX_PROBES)
+    with_probe_count<LO, M + 1>(m, f);
+}
+
 // out[2*j], out[2*j+1] = Re, Im <p_j|x> of this rank's share (n double2 elements), j < m: one pass over x and the probes on g workgroups, then
 // one workgroup that adds the block partials in block order.  d_part: g * 2m doubles.  (The drivers pass g = grid_for(n) and the handle's
-// stream: launch_probe_dots of hxv_lanczos.hip.)
+// stream: LzProbeSet::enqueue of hxv_lanczos.hip.)
 template <bool REAL>
 void launch_probe_dots(int g, hipStream_t st, int m, int64_t n, const double2* x, const LzProbes& pr, double* d_part, double* d_out) {
-  switch (m) {
-#define HXV_PROBE_CASE(M) \
-  case M:                 \
-    hipLaunchKernelGGL((lz_probe_dots<M, REAL>), dim3(g), dim3(256), 0, st, n, x, pr, d_part); \
-    break;
-    HXV_PROBE_CASE(1)
-    HXV_PROBE_CASE(2)
-    HXV_PROBE_CASE(3)
-    HXV_PROBE_CASE(4)
-    HXV_PROBE_CASE(5)
-    HXV_PROBE_CASE(6)
-    HXV_PROBE_CASE(7)
-    HXV_PROBE_CASE(8)
-#undef HXV_PROBE_CASE
-  }
+  with_probe_count<1>(m, [&](auto M) { hipLaunchKernelGGL((lz_probe_dots<M(), REAL>), dim3(g), dim3(256), 0, st, n, x, pr, d_part); });
   hipLaunchKernelGGL(lz_probe_final, dim3(1), dim3(256), 0, st, d_part, g, 2 * m, d_out);
 }
 // out[2*j], out[2*j+1] = <p_j|Re x>, <p_j|Im x> of this rank's share for the m REAL probes of a paired run: lz_probe_dots_pair<m> on g workgroups,
 // then lz_probe_final as above.  d_part: g * 2m doubles.
 inline void launch_probe_dots_pair(int g, hipStream_t st, int m, int64_t n, const double2* x, const LzRealProbes& pr, double* d_part, double* d_out) {
-  switch (m) {
-#define HXV_PROBE_CASE(M) \
-  case M:                 \
-    hipLaunchKernelGGL((lz_probe_dots_pair<M>), dim3(g), dim3(256), 0, st, n, x, pr, d_part); \
-    break;
-    HXV_PROBE_CASE(1)
-    HXV_PROBE_CASE(2)
-    HXV_PROBE_CASE(3)
-    HXV_PROBE_CASE(4)
-    HXV_PROBE_CASE(5)
-    HXV_PROBE_CASE(6)
-    HXV_PROBE_CASE(7)
-    HXV_PROBE_CASE(8)
-#undef HXV_PROBE_CASE
-  }
+  with_probe_count<1>(m, [&](auto M) { hipLaunchKernelGGL((lz_probe_dots_pair<M()>), dim3(g), dim3(256), 0, st, n, x, pr, d_part); });
   hipLaunchKernelGGL(lz_probe_final, dim3(1), dim3(256), 0, st, d_part, g, 2 * m, d_out);
 }
 

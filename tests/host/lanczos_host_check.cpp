@@ -10,6 +10,12 @@
 //   lanczos_host_check scale FILE  FILE: lines "nrm beta_1 beta_2 ...".  Per line: LzScale::begin(nrm), then next(beta_k) in turn; after begin
 //                                  and after every next one triple "s_cur beta_prev c()" (hex floats), all on one line
 //   lanczos_host_check norm X...   start_norm(X) for every argument (hex floats), one per line
+//   lanczos_host_check ritz FILE   FILE: matrices as for ql.  lowest_ritz, with the eigenvector and without, beside the sequence it stands for
+//                                  written out here: identity, tridiag_ql, std::min_element.  Per matrix one line:
+//                                    ok=<0|1> ok_ref=<0|1> same=<0|1> same_noy=<0|1> j=<index of the lowest eigenvalue> n=<n> e=<it>
+//                                  same: eigenvalue, index and vector have the bits of the written-out sequence; same_noy: so has the
+//                                  eigenvalue asked for without the vector (against tridiag_ql without z); after a failure only the flags count
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -79,6 +85,49 @@ static int run_ql(const char* path) {
   return 0;
 }
 
+static int run_ritz(const char* path) {
+  FILE* f = std::fopen(path, "r");
+  if (!f) {
+    std::fprintf(stderr, "cannot open %s\n", path);
+    return 2;
+  }
+  int n = 0;
+  while (std::fscanf(f, "%d", &n) == 1) {
+    if (n < 1 || n > 4096) {
+      std::fprintf(stderr, "bad n %d\n", n);
+      std::fclose(f);
+      return 2;
+    }
+    std::vector<double> al(n), be(n);
+    for (int pass = 0; pass < 2; ++pass)
+      for (int i = 0; i < n; ++i)
+        if (!read_double(f, pass ? &be[i] : &al[i])) {
+          std::fprintf(stderr, "bad number in %s\n", path);
+          std::fclose(f);
+          return 2;
+        }
+    // the sequence as hxv_lanczos_eigh wrote it out before the helper existed
+    std::vector<double> d = al, e = be, z((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i) z[i + (size_t)i * n] = 1.0;
+    const bool ok_ref = tridiag_ql(n, d, e, &z);
+    const int j_ref = (int)(std::min_element(d.begin(), d.end()) - d.begin());
+    std::vector<double> d2 = al, e2 = be;
+    const bool ok_ref2 = tridiag_ql(n, d2, e2, nullptr);
+    const double e_ref2 = *std::min_element(d2.begin(), d2.end());
+    double e_min = 0.0, e_noy = 0.0;
+    int j = -1;
+    std::vector<double> y;
+    const bool ok = lowest_ritz(al, be, &e_min, &y, &j);
+    const bool ok2 = lowest_ritz(al, be, &e_noy, nullptr);
+    const bool same = ok && ok_ref && j == j_ref && std::memcmp(&e_min, &d[j_ref], sizeof(double)) == 0 && y.size() == (size_t)n &&
+                      std::memcmp(y.data(), &z[(size_t)j_ref * n], (size_t)n * sizeof(double)) == 0;
+    const bool same_noy = ok2 && ok_ref2 && std::memcmp(&e_noy, &e_ref2, sizeof(double)) == 0;
+    std::printf("ok=%d ok_ref=%d same=%d same_noy=%d j=%d n=%d e=%a\n", (ok && ok2) ? 1 : 0, (ok_ref && ok_ref2) ? 1 : 0, same ? 1 : 0, same_noy ? 1 : 0, j, n, e_min);
+  }
+  std::fclose(f);
+  return 0;
+}
+
 static int run_scale(const char* path) {
   FILE* f = std::fopen(path, "r");
   if (!f) {
@@ -114,10 +163,11 @@ int main(int argc, char** argv) {
   const std::string mode = argc > 1 ? argv[1] : "";
   if (mode == "ql" && argc == 3) return run_ql(argv[2]);
   if (mode == "scale" && argc == 3) return run_scale(argv[2]);
+  if (mode == "ritz" && argc == 3) return run_ritz(argv[2]);
   if (mode == "norm" && argc >= 3) {
     for (int a = 2; a < argc; ++a) std::printf("%a\n", start_norm(std::strtod(argv[a], nullptr)));
     return 0;
   }
-  std::fprintf(stderr, "usage: lanczos_host_check ql FILE | scale FILE | norm X...\n");
+  std::fprintf(stderr, "usage: lanczos_host_check ql FILE | scale FILE | ritz FILE | norm X...\n");
   return 2;
 }

@@ -1,6 +1,6 @@
 """The host routines of the Lanczos drivers on the CPU (tests/host/lanczos_host_check.cpp over csrc/hxv_lanczos_host.hpp): tridiag_ql, which
 every driver's eigenvalues, Ritz vectors and Green's-function weights go through, LzScale, the host's copy of the fused recurrence's scale
-factors, and start_norm.  The program is stand-alone (its own main, no HIP); it is built plainly and with -fsanitize=address,undefined
+factors, start_norm, and lowest_ritz, the lowest Ritz pair hxv_lanczos_eigh takes from tridiag_ql.  The program is stand-alone (its own main, no HIP); it is built plainly and with -fsanitize=address,undefined
 and run directly, nothing is preloaded.
 
 tridiag_ql, over the matrix set of matrices(): the convergence flag is set, and with u = 2**-53 and tol = 8 n u max(|d|, |e|) -- the
@@ -14,7 +14,9 @@ those with.  A NaN entry returns false in bounded time.  n = 0 is outside tridia
 tests/test_gpu_lanczos_kernels.py asserts that every caller refuses nlanc < 1.
 LzScale: begin, next and c() against their definitions in long double, one rounding per operation.  start_norm: snaps exactly the doubles
 with |nrm - 1| <= 1e-14 (the difference is exact there; 1e-14 is the double nearest to it).
-Wall time: 5 tests in 3 s; 5 s when the sanitized program has to be built first."""
+lowest_ritz: eigenvalue, index and vector have the bits of the sequence it stands for (identity, tridiag_ql, std::min_element), written out in
+the program: n = 1, 2, 7, a degenerate lowest pair (the first of the equal eigenvalues is taken), n = 50; a NaN returns false.
+Wall time: 6 tests in 3 s; 5 s when the sanitized program has to be built first."""
 import subprocess
 from fractions import Fraction
 
@@ -185,6 +187,41 @@ def check_scale_and_norm(exe, tmp_path):
     assert p.returncode == 0 and np.isnan(float.fromhex(p.stdout.split()[0]))
 
 
+def check_lowest_ritz(exe, tmp_path):
+    mats = matrices()
+    rng = np.random.default_rng(3)
+    d7 = 2.0 * rng.normal(size=7)
+    cases = [mats["n1"], mats["n2"], (d7, np.concatenate([[0.0], 0.5 + rng.random(6)])),
+             # a degenerate lowest pair: two uncoupled copies of one 3 x 3 block (the first of the equal eigenvalues is taken) ...
+             (np.array([1.0, -2.0, 0.5, 1.0, -2.0, 0.5]), np.array([0.0, 1.5, 0.75, 0.0, 1.5, 0.75])),
+             # ... and a diagonal matrix with its lowest entry twice
+             (np.array([3.0, -1.0, 2.0, -1.0, 5.0]), np.zeros(5)), mats["zero6"], mats["random50"]]
+    rc, out, err = _run_ritz(exe, write_matrices(tmp_path / "ritz.txt", cases))
+    assert rc == 0 and _no_report(err), (rc, err[-3000:])
+    assert len(out) == len(cases)
+    for (d, e), r in zip(cases, out):
+        assert r["n"] == len(d) and r["ok"] == 1 and r["ok_ref"] == 1 and r["same"] == 1 and r["same_noy"] == 1, r
+        assert 0 <= r["j"] < len(d)
+    assert out[0]["e"] == 3.5 and out[0]["j"] == 0
+    assert out[4]["e"] == -1.0 and out[4]["j"] == 1                     # the first of the two equal lowest entries
+    assert abs(out[3]["e"] - lapack(*cases[3])[0]) <= bounds(*cases[3])[0]
+    # a NaN: false from the helper as from the written-out sequence, and nothing for the sanitizers to report
+    d, e = mats["random50"][0].copy(), mats["random50"][1].copy()
+    d[25] = np.nan
+    rc, out, err = _run_ritz(exe, write_matrices(tmp_path / "ritz_nan.txt", [(d, e), (np.array([1.0, np.nan]), np.array([0.0, 1.0]))]))
+    assert rc == 0 and _no_report(err), (rc, err[-3000:])
+    assert [(r["ok"], r["ok_ref"]) for r in out] == [(0, 0), (0, 0)], out
+
+
+def _run_ritz(exe, path):
+    p = subprocess.run([str(exe), "ritz", str(path)], capture_output=True, text=True, timeout=120)
+    out = []
+    for line in p.stdout.splitlines():
+        r = {k: v for k, v in (t.split("=") for t in line.split())}
+        out.append({k: (float.fromhex(v) if k == "e" else int(v)) for k, v in r.items()})
+    return p.returncode, out, p.stderr
+
+
 # ---- the tests ------------------------------------------------------------------------------------------------------------------------------
 def test_tridiag_ql_plain_build(built, tmp_path):
     check_ql(built.build_lanczos_host_check(), tmp_path)
@@ -198,8 +235,12 @@ def test_lzscale_and_start_norm_plain_build(built, tmp_path):
     check_scale_and_norm(built.build_lanczos_host_check(), tmp_path)
 
 
+def test_lowest_ritz_plain_build(built, tmp_path):
+    check_lowest_ritz(built.build_lanczos_host_check(), tmp_path)
+
+
 def test_host_routines_under_asan_and_ubsan(built, tmp_path):
-    """the same three checks with the program compiled with -fsanitize=address,undefined -fno-sanitize-recover=undefined: exit 0 and no
+    """the same four checks with the program compiled with -fsanitize=address,undefined -fno-sanitize-recover=undefined: exit 0 and no
     sanitizer report.  A stand-alone program, run directly; not on a GPU machine."""
     import torch
 
@@ -209,6 +250,7 @@ def test_host_routines_under_asan_and_ubsan(built, tmp_path):
     check_ql(exe, tmp_path)
     check_nan(exe, tmp_path)
     check_scale_and_norm(exe, tmp_path)
+    check_lowest_ritz(exe, tmp_path)
 
 
 def test_bounds_refuse_a_wrong_answer(built, tmp_path):
